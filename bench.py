@@ -17,8 +17,17 @@ the gradient all-reduce and the SGD update).  The timed loop drives the trainer'
 W untimed warm-up steps, then EXACTLY K timed steps bracketed by barrier + device sync (the clock
 stops at each rank's closing device sync, before the closing barrier); the MAX time over ranks is
 reported by rank 0 as one JSON line, together with a post-run check that the parameters are
-bit-identical on every replica.  The first timed execution's input indices are prefetched before
-the clock starts (input pipeline prefetch depth: one execution).
+bit-identical on every replica (it certifies the N > 1 figure; one replica has nothing to compare).
+The first timed execution's input indices are prefetched before the clock starts (input pipeline
+prefetch depth: one execution).
+
+A plain run does only that: set up, warm up, time the K steps, print the line.  ``--full`` adds what
+the headline figure does not need: the modelled multi-GPU prediction (``predicted``).
+``--dump-outputs DIR`` writes what the timed path left after its last
+step as ``DIR/<name>.npy`` (rank 0): ``weights`` (the flat float32 parameter slab after W + K SGD
+steps) and, in float64, ``loss`` and each compiled metric as the steps accumulated them on the device.
+The data, the initial parameters and the shuffle order (``--seed``) are the same in every run, so two
+builds can be compared output for output.
 
 Without a launcher and N > 1 the script starts N-1 extra replica processes of itself before any
 GPU call (MirroredStrategy(devices=[/gpu:0 .. /gpu:N-1])).  With TDL_SHARE_GPU=1 the N replicas
@@ -36,16 +45,29 @@ sys.path.insert(0, ROOT)
 
 
 def _spe(K: int, cap: int = 25) -> int:
-    """Steps per execution: the largest divisor of K that is <= cap (one graph launch per
-    execution; the timed region replays K / spe graphs).  Measured on one MI355X
+    """Steps per execution: ``cap``, or K when K is smaller (one graph launch per execution; the
+    timed region replays K // spe graphs of spe steps and, when K is no multiple, one last graph of
+    the K % spe steps left, captured ahead of the clock like the others).  The largest divisor of K
+    used to be taken: a K with none near the cap, a prime for one, then ran one step per graph,
+    bound by the host's launches and 2-3 x slower from run to run (36-69 us/step at K=10007
+    against 23.3 at K=40000).  Measured on one MI355X
     (profiles/mnist_bench_spe_sweep_r5.txt): at K=1000, 20-25 steps (40-50 kernel nodes) per graph
     run 0.5 % faster than 50; at K=20 one graph of 20 beats 2 x 10 / 4 x 5 (every graph launch
     costs the region its own submission latency); round 2's sweep put 100-1000 steps per graph
     5 % behind 50 (profiles/mnist_bench_spe_sweep_r2.txt)."""
-    for d in range(min(K, cap), 0, -1):
-        if K % d == 0:
-            return d
-    return 1
+    return max(1, min(K, cap))
+
+
+def _dump_outputs(out_dir: str, trainer, logs) -> None:
+    """What the timed path left after its last step: ``weights.npy``, the flat parameter slab the
+    optimizer updates wrote (float32), and one float64 ``<name>.npy`` per entry of the trainer's
+    logs (the loss and the metrics the steps accumulated on the device)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "weights.npy"), trainer.W.detach().float().cpu().numpy())
+    for name, v in logs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray([v], dtype=np.float64))
 
 
 def main():
@@ -67,6 +89,12 @@ def main():
                          "any model gets (TDL_DISABLE_FUSED=1) -- measures the cliff a model change meets")
     ap.add_argument("--variant", choices=["reference", "same", "dropout"], default="reference",
                     help="(generic engine) the reference CNN, with padding='same' convs, or with a Dropout layer")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline figure does not need: the modelled multi-GPU prediction")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the parameters and the metric sums they left as DIR/<name>.npy")
+    ap.add_argument("--seed", type=int, default=0,
+                    help="seed of the initial parameters and of the input pipeline's shuffle (replica r: seed + r)")
     args = ap.parse_args()
     if args.engine == "generic":
         os.environ["TDL_DISABLE_FUSED"] = "1"
@@ -79,6 +107,7 @@ def main():
 
     import tensorflow_distributed_learning_amd as tdl
     from tensorflow_distributed_learning_amd.data import tfds
+    from tensorflow_distributed_learning_amd.keras import initializers
     from tensorflow_distributed_learning_amd.models.mnist_cnn import build_mnist_cnn
     from tensorflow_distributed_learning_amd.parallel import consistency
     from tensorflow_distributed_learning_amd.parallel.launch import ipc_mode
@@ -101,6 +130,10 @@ def main():
     K, W = args.steps, args.warmup
     spe = args.steps_per_execution or _spe(K)
 
+    # the same initial parameters and the same batches in every run (replicas keep distinct shuffle
+    # orders, as unseeded ones had)
+    initializers.set_seed(args.seed)
+    tdl.data.set_global_seed(args.seed + rank)
     # synthetic MNIST-shaped data (no network): the reference's input pipeline
     (ds_all, info) = tfds.load("mnist", as_supervised=True, with_info=True)
 
@@ -210,13 +243,17 @@ def main():
         a = np.array(ht[-max(1, K // max(1, spe)):]) * 1e6
         print(f"host us per execution (take, graph+upload, launch): median {np.median(a, 0).round(1).tolist()} "
               f"max {a.max(0).round(1).tolist()}", file=sys.stderr)
-    from tensorflow_distributed_learning_amd.parallel import bucketing
+    extra = {}
+    if args.full:
+        from tensorflow_distributed_learning_amd.parallel import bucketing
 
-    # modelled multi-GPU prediction (parallel/bucketing.py), from this run's step time at N = 1
-    # and the recorded one-GPU number otherwise -- the driver's SCALE run checks it
-    predicted = bucketing.predict_mnist_scaling(
-        dt / K * 1e3 if R == 1 and args.per_replica_batch == 64 else bucketing.MNIST_T1_MS_RECORDED,
-        twoshot_min_r=int(os.environ.get("TDL_FX_TWOSHOT_MIN_R", "3"))) if fused else None
+        # modelled multi-GPU prediction (parallel/bucketing.py), from this run's step time at N = 1
+        # and the recorded one-GPU number otherwise -- the driver's SCALE run checks it
+        extra["predicted"] = bucketing.predict_mnist_scaling(
+            dt / K * 1e3 if R == 1 and args.per_replica_batch == 64 else bucketing.MNIST_T1_MS_RECORDED,
+            twoshot_min_r=int(os.environ.get("TDL_FX_TWOSHOT_MIN_R", "3"))) if fused else None
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, trainer, logs)
     if rank == 0:
         print(json.dumps({
             "metric": "images/sec (whole node) MNIST CNN global_batch=64*N",
@@ -257,7 +294,7 @@ def main():
                        "rank_spread_pct": round(100.0 * (max(per_rank) - min(per_rank)) / max(per_rank), 2),
                        "fallbacks": list(getattr(trainer, "fallbacks", [])) + (
                            [f"xgmi: {comm.xgmi_reason}"] if getattr(comm, "xgmi_reason", "") else [])},
-            "predicted": predicted,
+            **extra,
         }), flush=True)
     strategy.shutdown()
     if not identical:

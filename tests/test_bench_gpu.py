@@ -30,6 +30,57 @@ def test_bench_one_gpu_is_one_replica():
     assert d["value"] > 0 and d["steps"] == 20
 
 
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without the
+    modelled prediction (--full adds it); --dump-outputs writes what the steps left (the parameter
+    slab, the loss and the metric), and a second run with the same arguments sees the same inputs:
+    the parameters come out bit-identical (no floating-point atomics on their path), the loss within
+    the reordering error of its float32 atomic sum (25 steps x 64 terms, each <= 2^-24 relative:
+    1600 * 6e-8 ~ 1e-4)."""
+    import numpy as np
+
+    outs = []
+    for name in ("a", "b"):
+        out = tmp_path / name
+        d = _bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)] +
+                   (["--full"] if name == "b" else []), HIP_VISIBLE_DEVICES="0")
+        assert d["steps"] == 20 and d["warmup"] == 5 and d["config"]["steps_per_execution"] == 20
+        assert d["unit"] == "images/sec" and d["higher_is_better"] is True and d["dtype"] == "fp32"
+        assert d["metric"].startswith("images/sec") and d["value"] > 0 and d["ms_per_step"] > 0
+        # value and ms_per_step describe the same timed region (ms_per_step is rounded to 1e-5 ms)
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / 64 - 1.0) < 2e-3, d
+        if name == "a":
+            assert "predicted" not in d, d
+        else:
+            assert d["predicted"]["label"] == "modelled, not measured" and d["predicted"]["t1_ms"] > 0, d
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["loss.npy", "sparse_categorical_accuracy.npy", "weights.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+        w, loss = np.load(out / "weights.npy"), np.load(out / "loss.npy")
+        assert w.dtype == np.float32 and w.ndim == 1 and w.size >= 225034 and np.isfinite(w).all()  # (padded slab)
+        assert loss.dtype == np.float64 and loss.shape == (1,) and round(float(loss[0]), 4) == d["config"]["final_loss"]
+        outs.append((w, loss, np.load(out / "sparse_categorical_accuracy.npy")))
+    (wa, la, aa), (wb, lb, ab) = outs
+    assert np.array_equal(wa, wb)
+    np.testing.assert_allclose(la, lb, rtol=1e-4)
+    np.testing.assert_array_equal(aa, ab)
+
+
+def test_bench_step_count_without_a_divisor_near_the_cap(tmp_path):
+    """--steps 57 has no divisor near 25 steps per graph: the run replays 2 graphs of 25 and one of
+    the 7 steps left (not 57 graphs of one step, or 3 of 19), times exactly 57 steps, and leaves
+    bit-identical parameters to a run of the same 57 steps grouped 3 x 19."""
+    import numpy as np
+
+    a = _bench(["--gpus", "1", "--steps", "57", "--warmup", "3", "--dump-outputs", str(tmp_path / "a")],
+               HIP_VISIBLE_DEVICES="0")
+    b = _bench(["--gpus", "1", "--steps", "57", "--warmup", "3", "--steps-per-execution", "19", "--dump-outputs",
+                str(tmp_path / "b")], HIP_VISIBLE_DEVICES="0")
+    assert a["steps"] == 57 and a["config"]["steps_per_execution"] == 25 and a["config"]["graph_captured"], a
+    assert b["steps"] == 57 and b["config"]["steps_per_execution"] == 19, b
+    assert np.array_equal(np.load(tmp_path / "a" / "weights.npy"), np.load(tmp_path / "b" / "weights.npy"))
+
+
 def test_bench_two_replicas_self_launched_shared_gpu():
     d = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5"], TDL_SHARE_GPU="1")
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 128
