@@ -23,6 +23,12 @@ void check_cuda_f32(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == at::kFloat, name, " must be float32");
 }
 
+// an optimizer kernel's slab operand: read and written with 16-byte vector accesses
+void check_slab_f32(const at::Tensor& t, const char* name) {
+  check_cuda_f32(t, name);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
 // Owns the scratch buffers and the argument block of one replica's fused MNIST step.
 class MnistStep {
  public:
@@ -264,17 +270,17 @@ class MnistStep {
 };
 
 void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad) {
-  check_cuda_f32(w, "w");
-  check_cuda_f32(g, "g");
+  check_slab_f32(w, "w");
+  check_slab_f32(g, "g");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel());
   tdl::sgd_apply(w.data_ptr<float>(), g.data_ptr<float>(), lr.data_ptr<float>(), w.numel(), cur_stream(), zero_grad);
 }
 
 void sgd_momentum(at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor lr, double m, bool nesterov, bool zero_grad) {
-  check_cuda_f32(w, "w");
-  check_cuda_f32(g, "g");
-  check_cuda_f32(v, "v");
+  check_slab_f32(w, "w");
+  check_slab_f32(g, "g");
+  check_slab_f32(v, "v");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel() && v.numel() == w.numel());
   tdl::sgd_momentum_apply(w.data_ptr<float>(), g.data_ptr<float>(), v.data_ptr<float>(), lr.data_ptr<float>(),
@@ -284,12 +290,13 @@ void sgd_momentum(at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor lr, doubl
 // Flat-slab Adam / AdamW (+AMSGrad): state m, v (vhat), device lr and execution-start step t0
 void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<at::Tensor> vhat, at::Tensor lr,
           at::Tensor t0, int64_t t_add, double b1, double b2, double eps, double wd) {
-  for (auto* t : {&w, &g, &m, &v, &lr, &t0}) check_cuda_f32(*t, "adam operand");
+  for (auto* t : {&w, &g, &m, &v}) check_slab_f32(*t, "adam operand");
+  for (auto* t : {&lr, &t0}) check_cuda_f32(*t, "adam operand");
   TORCH_CHECK(g.numel() == w.numel() && m.numel() == w.numel() && v.numel() == w.numel());
   tdl::OptimArgs a{};
   a.w = w.data_ptr<float>(); a.g = g.data_ptr<float>(); a.s0 = m.data_ptr<float>(); a.s1 = v.data_ptr<float>();
   if (vhat.has_value()) {
-    check_cuda_f32(*vhat, "vhat");
+    check_slab_f32(*vhat, "vhat");
     TORCH_CHECK(vhat->numel() == w.numel());
     a.s2 = vhat->data_ptr<float>();
     a.flags = 1;
@@ -302,19 +309,21 @@ void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<
 // Flat-slab RMSprop (+momentum, centered)
 void rmsprop(at::Tensor w, at::Tensor g, at::Tensor rms, c10::optional<at::Tensor> mom, c10::optional<at::Tensor> mg,
              at::Tensor lr, double rho, double momentum, double eps) {
-  for (auto* t : {&w, &g, &rms, &lr}) check_cuda_f32(*t, "rmsprop operand");
+  for (auto* t : {&w, &g, &rms}) check_slab_f32(*t, "rmsprop operand");
+  check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && rms.numel() == w.numel());
   tdl::OptimArgs a{};
   a.w = w.data_ptr<float>(); a.g = g.data_ptr<float>(); a.s0 = rms.data_ptr<float>();
-  if (mom.has_value()) { check_cuda_f32(*mom, "mom"); TORCH_CHECK(mom->numel() == w.numel()); a.s1 = mom->data_ptr<float>(); a.flags |= 1; }
-  if (mg.has_value()) { check_cuda_f32(*mg, "mg"); TORCH_CHECK(mg->numel() == w.numel()); a.s2 = mg->data_ptr<float>(); a.flags |= 2; }
+  if (mom.has_value()) { check_slab_f32(*mom, "mom"); TORCH_CHECK(mom->numel() == w.numel()); a.s1 = mom->data_ptr<float>(); a.flags |= 1; }
+  if (mg.has_value()) { check_slab_f32(*mg, "mg"); TORCH_CHECK(mg->numel() == w.numel()); a.s2 = mg->data_ptr<float>(); a.flags |= 2; }
   a.lr = lr.data_ptr<float>(); a.n = w.numel(); a.b1 = (float)rho; a.b2 = (float)momentum; a.eps = (float)eps;
   tdl::rmsprop_apply(a, cur_stream());
 }
 
 // Flat-slab Adagrad
 void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double eps) {
-  for (auto* t : {&w, &g, &acc, &lr}) check_cuda_f32(*t, "adagrad operand");
+  for (auto* t : {&w, &g, &acc}) check_slab_f32(*t, "adagrad operand");
+  check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && acc.numel() == w.numel());
   tdl::OptimArgs a{};
   a.w = w.data_ptr<float>(); a.g = g.data_ptr<float>(); a.s0 = acc.data_ptr<float>();

@@ -16,6 +16,7 @@
 // consecutive n of one m (16-B f32 / 8-B bf16 stores).  Edges are zero-filled on load and masked
 // on store (M, N, K multiples of 8 for the 16-B loads; N multiple of 4 for the stores).
 #include "kernels/gemm.h"
+#include "kernels/common.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -171,14 +172,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_bf16(Gemm g) {
       if (g.bias) v += *reinterpret_cast<const f4v*>(g.bias + n);
       const long long o = (long long)m * g.ldc + n;
       if (g.c16) {
-        uint32_t u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          u[e] = __float_as_uint(v[e]);
-          u[e] += 0x7fffu + ((u[e] >> 16) & 1u);
-        }
-        *reinterpret_cast<uint2*>(g.c16 + o) =
-            make_uint2((u[0] >> 16) | (u[1] & 0xffff0000u), (u[2] >> 16) | (u[3] & 0xffff0000u));
+        *reinterpret_cast<uint2*>(g.c16 + o) = make_uint2(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]));
       } else {
         f4v* p = reinterpret_cast<f4v*>(g.c32 + o);
         *p = g.accumulate ? *p + v : v;
@@ -192,6 +186,7 @@ bool gemm_bf16_supported(int M, int N, int K) { return M > 0 && N > 0 && K > 0 &
 
 void gemm_bf16(int ta, int tb, const void* a, long long lda, const void* b, long long ldb, int M, int N, int K,
                float* c32, void* c16, long long ldc, const float* bias, float alpha, bool accumulate, hipStream_t s) {
+  if (M <= 0 || N <= 0) return;  // (an empty grid is a launch error nobody reads)
   Gemm g{static_cast<const uint16_t*>(a), static_cast<const uint16_t*>(b), lda, ldb, M, N, K, c32,
          static_cast<uint16_t*>(c16), ldc, bias, alpha, accumulate ? 1 : 0};
   const dim3 grid(((M + TM - 1) / TM) * ((N + TN - 1) / TN)), blk(256);
@@ -229,12 +224,7 @@ __global__ __launch_bounds__(256) void k_gap_fwd(const uint16_t* __restrict__ x,
   const float inv = 1.f / (float)HW;
   uint32_t o[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    uint32_t lo = __float_as_uint(s[2 * j] * inv), hi = __float_as_uint(s[2 * j + 1] * inv);
-    lo += 0x7fffu + ((lo >> 16) & 1u);
-    hi += 0x7fffu + ((hi >> 16) & 1u);
-    o[j] = (lo >> 16) | (hi & 0xffff0000u);
-  }
+  for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(s[2 * j] * inv, s[2 * j + 1] * inv);
   *reinterpret_cast<u32x4*>(y + (long long)n * C + cg * 8) = u32x4{o[0], o[1], o[2], o[3]};
 }
 
@@ -251,13 +241,8 @@ __global__ __launch_bounds__(256) void k_gap_bwd(const uint16_t* __restrict__ dy
     const u32x4 v = *reinterpret_cast<const u32x4*>(dy + (long long)n * C + cg * 8);
     uint32_t o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t lo = __float_as_uint(__uint_as_float(v[j] << 16) * inv);
-      uint32_t hi = __float_as_uint(__uint_as_float(v[j] & 0xffff0000u) * inv);
-      lo += 0x7fffu + ((lo >> 16) & 1u);
-      hi += 0x7fffu + ((hi >> 16) & 1u);
-      o[j] = (lo >> 16) | (hi & 0xffff0000u);
-    }
+    for (int j = 0; j < 4; ++j)
+      o[j] = pack_bf16x2(__uint_as_float(v[j] << 16) * inv, __uint_as_float(v[j] & 0xffff0000u) * inv);
     *reinterpret_cast<u32x4*>(dx + np * C + cg * 8) = u32x4{o[0], o[1], o[2], o[3]};
   }
 }
@@ -266,12 +251,14 @@ __global__ __launch_bounds__(256) void k_gap_bwd(const uint16_t* __restrict__ dy
 
 void gap_fwd_bf16(const void* x, void* y, int N, int HW, int C, hipStream_t s) {
   const long long threads = (long long)N * (C / 8);
+  if (threads <= 0) return;
   hipLaunchKernelGGL(k_gap_fwd, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
                      static_cast<const uint16_t*>(x), static_cast<uint16_t*>(y), N, HW, C);
 }
 
 void gap_bwd_bf16(const void* dy, void* dx, int N, int HW, int C, hipStream_t s) {
   const long long total = (long long)N * HW * (C / 8);
+  if (total <= 0) return;
   const long long blocks = std::min<long long>((total + 255) / 256, 256 * 16);
   hipLaunchKernelGGL(k_gap_bwd, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint16_t*>(dy),
                      static_cast<uint16_t*>(dx), N, HW, C);
@@ -532,18 +519,21 @@ void xent_head(const float* z, const long long* labels, int N, int K, double gn,
                          lt_count, acc_total, acc_count);
     return;
   }
-  hipLaunchKernelGGL(k_xent_rows, dim3((N + 3) / 4), dim3(256), 0, s, z, labels, N, K, gn, dz, rows_ws, rows_ws + N);
+  if (N > 0)  // (no rows: k_xent_finish alone writes a zero loss and leaves the sums as they are)
+    hipLaunchKernelGGL(k_xent_rows, dim3((N + 3) / 4), dim3(256), 0, s, z, labels, N, K, gn, dz, rows_ws, rows_ws + N);
   hipLaunchKernelGGL(k_xent_finish, dim3(1), dim3(1024), 0, s, rows_ws, rows_ws + N, N, gn, loss_out, lt_total,
                      lt_count, acc_total, acc_count);
 }
 
 void softmax_xent_fwd(const float* z, const long long* labels, int N, int K, float* loss, float* lse, hipStream_t s) {
+  if (N <= 0) return;
   hipLaunchKernelGGL(k_softmax_xent, dim3((N + 3) / 4), dim3(256), 0, s, z, labels, N, K, loss, lse, nullptr,
                      nullptr);
 }
 
 void softmax_xent_bwd(const float* z, const long long* labels, int N, int K, const float* g, float* dz,
                       hipStream_t s) {
+  if (N <= 0) return;
   hipLaunchKernelGGL(k_softmax_xent, dim3((N + 3) / 4), dim3(256), 0, s, z, labels, N, K, nullptr, nullptr, g, dz);
 }
 

@@ -1764,12 +1764,14 @@ void mnist_finalize_x(const MnistArgs& a, bool apply_sgd, hipStream_t s) {
   }
 }
 void sgd_apply(float* w, const float* g, const float* lr, int64_t n, hipStream_t s, bool zero_g) {
+  if (n <= 0) return;
   const int64_t nt = (n + 3) / 4;
   hipLaunchKernelGGL(k_sgd, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w, g, lr, n,
                      zero_g ? const_cast<float*>(g) : nullptr);
 }
 void sgd_momentum_apply(float* w, const float* g, float* v, const float* lr, float momentum, bool nesterov,
                         int64_t n, hipStream_t s, bool zero_g) {
+  if (n <= 0) return;
   const int64_t nt = (n + 3) / 4;
   hipLaunchKernelGGL(k_sgd_momentum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w, g, v, lr, momentum,
                      nesterov ? 1 : 0, n, zero_g ? const_cast<float*>(g) : nullptr);

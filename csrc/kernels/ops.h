@@ -5,16 +5,10 @@
 
 namespace tdl {
 
-// out[r, :] = src[idx[r], :] * scale   (row gather of a device-resident dataset; f32 rows)
+// (out[r, :], out_lab[r]) = (src[idx[r], :], lab[idx[r]]): a batch of a device-resident dataset (f32 rows,
+// 4- or 8-byte labels) in one launch
 void gather_xy(const float* src, const void* lab, const int* idx, float* out, void* out_lab, int64_t rows,
                int64_t row_elems, int lab_bytes, hipStream_t s);
-void gather_rows_f32(const float* src, const int* idx, float* out, int64_t rows, int64_t row_elems, float scale,
-                     hipStream_t s);
-// out[r, :] = float(src[idx[r], :]) * scale   (uint8 images -> f32, the reference's map(scale))
-void gather_rows_u8(const uint8_t* src, const int* idx, float* out, int64_t rows, int64_t row_elems, float scale,
-                    hipStream_t s);
-// out[r] = src[idx[r]]   (labels)
-void gather_i32(const int* src, const int* idx, int* out, int64_t rows, hipStream_t s);
 
 // Weight-slab cast with transposes: for every 64 x 64 tile listed in `tiles` (int4: entry, row
 // tile, column tile, unused) of every entry e (int4 in `entries`: src offset, dst offset, R, K),

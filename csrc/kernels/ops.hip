@@ -7,39 +7,6 @@
 
 namespace tdl {
 
-__global__ __launch_bounds__(256) void k_gather_rows_f32(const float* __restrict__ src, const int* __restrict__ idx,
-                                                         float* __restrict__ out, int64_t row_elems, float scale) {
-  const int64_t r = blockIdx.x;
-  const float* s = src + (int64_t)idx[r] * row_elems;
-  float* o = out + r * row_elems;
-  if ((row_elems & 3) == 0) {
-    for (int64_t e = threadIdx.x * 4; e < row_elems; e += 1024) st4(o + e, ld4(s + e) * scale);
-  } else {
-    for (int64_t e = threadIdx.x; e < row_elems; e += 256) o[e] = s[e] * scale;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gather_rows_u8(const uint8_t* __restrict__ src, const int* __restrict__ idx,
-                                                        float* __restrict__ out, int64_t row_elems, float scale) {
-  const int64_t r = blockIdx.x;
-  const uint8_t* s = src + (int64_t)idx[r] * row_elems;
-  float* o = out + r * row_elems;
-  if ((row_elems & 3) == 0 && ((uintptr_t)s & 3) == 0) {
-    for (int64_t e = threadIdx.x * 4; e < row_elems; e += 1024) {
-      const unsigned v = *reinterpret_cast<const unsigned*>(s + e);
-      st4(o + e, f4{(float)(v & 255), (float)((v >> 8) & 255), (float)((v >> 16) & 255), (float)(v >> 24)} * scale);
-    }
-  } else {
-    for (int64_t e = threadIdx.x; e < row_elems; e += 256) o[e] = (float)s[e] * scale;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_gather_i32(const int* __restrict__ src, const int* __restrict__ idx,
-                                                    int* __restrict__ out, int64_t rows) {
-  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (r < rows) out[r] = src[idx[r]];
-}
-
 // a batch of (f32 feature row, label) pairs of a device-resident dataset in ONE launch (the generic
 // engine's device input path): workgroup r copies row idx[r] and its thread 0 the label (4 or 8 bytes)
 __global__ __launch_bounds__(256) void k_gather_xy(const float* __restrict__ src, const void* __restrict__ lab,
@@ -69,21 +36,6 @@ void gather_xy(const float* src, const void* lab, const int* idx, float* out, vo
                      lab_bytes);
 }
 
-void gather_rows_f32(const float* src, const int* idx, float* out, int64_t rows, int64_t row_elems, float scale,
-                     hipStream_t s) {
-  if (rows == 0) return;
-  hipLaunchKernelGGL(k_gather_rows_f32, dim3((unsigned)rows), dim3(256), 0, s, src, idx, out, row_elems, scale);
-}
-void gather_rows_u8(const uint8_t* src, const int* idx, float* out, int64_t rows, int64_t row_elems, float scale,
-                    hipStream_t s) {
-  if (rows == 0) return;
-  hipLaunchKernelGGL(k_gather_rows_u8, dim3((unsigned)rows), dim3(256), 0, s, src, idx, out, row_elems, scale);
-}
-void gather_i32(const int* src, const int* idx, int* out, int64_t rows, hipStream_t s) {
-  if (rows == 0) return;
-  hipLaunchKernelGGL(k_gather_i32, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, src, idx, out, rows);
-}
-
 namespace {
 
 __global__ __launch_bounds__(256) void k_slab_transpose_bf16(const float* __restrict__ src, uint16_t* __restrict__ dst,
@@ -108,9 +60,7 @@ __global__ __launch_bounds__(256) void k_slab_transpose_bf16(const float* __rest
   for (int i = 0; i < 16; ++i) {
     const int k = (tid >> 6) + 4 * i;
     if (k0 + k < K && r0 + rc < R) {
-      uint32_t u = __float_as_uint(t[rc][k]);
-      u += 0x7fffu + ((u >> 16) & 1u);
-      dst[(long long)e.y + (long long)(k0 + k) * R + r0 + rc] = (uint16_t)(u >> 16);
+      dst[(long long)e.y + (long long)(k0 + k) * R + r0 + rc] = (uint16_t)pack_bf16x2(t[rc][k], 0.f);
     }
   }
 }
@@ -135,12 +85,7 @@ __global__ __launch_bounds__(256) void k_cast_bf16(const float* __restrict__ src
     const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
     uint32_t o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      uint32_t lo = __float_as_uint(f[2 * j]), hi = __float_as_uint(f[2 * j + 1]);
-      lo += 0x7fffu + ((lo >> 16) & 1u);
-      hi += 0x7fffu + ((hi >> 16) & 1u);
-      o[j] = (lo >> 16) | (hi & 0xffff0000u);
-    }
+    for (int j = 0; j < 4; ++j) o[j] = pack_bf16x2(f[2 * j], f[2 * j + 1]);  // (keeps NaN: a diverged slab stays NaN)
     reinterpret_cast<uint4*>(dst)[v] = make_uint4(o[0], o[1], o[2], o[3]);
   }
 }

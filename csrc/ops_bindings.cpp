@@ -51,34 +51,6 @@ std::vector<at::Tensor> gather_xy(at::Tensor X, at::Tensor Y, at::Tensor idx) {
   return {x, y};
 }
 
-at::Tensor gather_rows(at::Tensor src, at::Tensor idx, double scale) {
-  TORCH_CHECK(src.is_cuda() && idx.is_cuda(), "gather_rows: GPU tensors expected");
-  TORCH_CHECK(src.is_contiguous() && idx.is_contiguous(), "gather_rows: contiguous tensors expected");
-  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 1, "gather_rows: idx must be int32 [n]");
-  const int64_t rows = idx.numel();
-  const int64_t row_elems = src.numel() / std::max<int64_t>(src.size(0), 1);
-  std::vector<int64_t> shape(src.sizes().begin(), src.sizes().end());
-  shape[0] = rows;
-  auto out = fresh(shape, src.options().dtype(at::kFloat));
-  if (src.scalar_type() == at::kFloat) {
-    tdl::gather_rows_f32(src.data_ptr<float>(), idx.data_ptr<int>(), out.data_ptr<float>(), rows, row_elems,
-                         (float)scale, cur_stream());
-  } else if (src.scalar_type() == at::kByte) {
-    tdl::gather_rows_u8(src.data_ptr<uint8_t>(), idx.data_ptr<int>(), out.data_ptr<float>(), rows, row_elems,
-                        (float)scale, cur_stream());
-  } else {
-    TORCH_CHECK(false, "gather_rows: float32 or uint8 source expected");
-  }
-  return out;
-}
-
-at::Tensor gather_labels(at::Tensor src, at::Tensor idx) {
-  TORCH_CHECK(src.is_cuda() && idx.is_cuda() && src.scalar_type() == at::kInt && idx.scalar_type() == at::kInt,
-              "gather_labels: int32 GPU tensors expected");
-  auto out = fresh({idx.numel()}, src.options());
-  tdl::gather_i32(src.data_ptr<int>(), idx.data_ptr<int>(), out.data_ptr<int>(), idx.numel(), cur_stream());
-  return out;
-}
 tdl::BnDType bn_dtype(const at::Tensor& x) {
   if (x.scalar_type() == at::kFloat) return tdl::BnDType::kF32;
   TORCH_CHECK(x.scalar_type() == at::kBFloat16, "batch_norm: float32 or bfloat16 activations expected");
@@ -951,6 +923,9 @@ at::Tensor gap_bwd(at::Tensor dy, int64_t h, int64_t w) {
   tdl::gap_bwd_bf16(dy.data_ptr(), dx.data_ptr(), (int)dy.size(0), (int)(h * w), (int)dy.size(1), cur_stream());
   return dx;
 }
+// Sparse softmax cross-entropy (xent_fwd / xent_bwd / xent_head).  A label outside [0, K) is not an error:
+// its row contributes no loss, its dz is the plain softmax (no one-hot term), and xent_head counts the row
+// in `count` but never as correct.  (Parity of this case with TF is not pinned and not claimed.)
 std::vector<at::Tensor> xent_fwd(at::Tensor z, at::Tensor labels) {
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == at::kFloat && z.dim() == 2, "xent: f32 [N][K] logits");
   TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == at::kLong &&
@@ -991,7 +966,8 @@ std::vector<at::Tensor> xent_head(at::Tensor z, at::Tensor labels, double gn, c1
 
 at::Tensor xent_bwd(at::Tensor z, at::Tensor labels, at::Tensor g) {
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == at::kFloat && z.dim() == 2, "xent: f32 [N][K] logits");
-  TORCH_CHECK(labels.is_contiguous() && labels.scalar_type() == at::kLong && labels.numel() == z.size(0), "xent: labels");
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == at::kLong &&
+                  labels.numel() == z.size(0), "xent: int64 [N] GPU labels");
   TORCH_CHECK(g.is_cuda() && g.is_contiguous() && g.scalar_type() == at::kFloat && g.numel() == z.size(0), "xent: g");
   auto dz = fresh(z.sizes(), z.options());
   tdl::softmax_xent_bwd(z.data_ptr<float>(), reinterpret_cast<const long long*>(labels.data_ptr<int64_t>()), (int)z.size(0), (int)z.size(1),
@@ -1098,8 +1074,6 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("h"), pybind11::arg("wd"), pybind11::arg("pt"),
         pybind11::arg("pl"), pybind11::arg("residual") = pybind11::none());
   m.def("gather_xy", &gather_xy, "a batch of (feature row, label) pairs of a device-resident dataset, one launch");
-  m.def("gather_rows", &gather_rows, "row gather (+u8->f32 scale) of a device-resident dataset");
-  m.def("gather_labels", &gather_labels);
   m.def("bn_forward_train", &bn_forward_train, "NHWC batch-norm training forward (+relu)", pybind11::arg("x"),
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("moving_mean"), pybind11::arg("moving_var"),
         pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("relu") = false,

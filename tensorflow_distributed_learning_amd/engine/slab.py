@@ -95,3 +95,20 @@ class SlabLayout:
             out.append((0, end))
         del bounds
         return out
+
+
+def transpose_tables(specs: Sequence[VarSpec], offsets: Sequence[int]) -> Tuple[List[List[int]], List[List[int]]]:
+    """Tables of the one-launch HWIO f32 -> OHWI bf16 slab transpose (csrc/kernels/ops.hip
+    k_slab_transpose_bf16) for the 4-D (conv kernel) variables among ``specs`` at slab ``offsets``:
+    ``entries`` [E][4] = (src offset, dst offset, R = KH*KW*C, K) and ``tiles`` [T][4] = (entry,
+    64-row tile of R, 64-column tile of K, 0), one workgroup per tile."""
+    entries: List[List[int]] = []
+    tiles: List[List[int]] = []
+    for spec, off in zip(specs, offsets):
+        if len(spec.shape) != 4:
+            continue
+        R, K = spec.shape[0] * spec.shape[1] * spec.shape[2], spec.shape[3]
+        e = len(entries)
+        entries.append([off, off, R, K])
+        tiles += [[e, a, b, 0] for a in range((R + 63) // 64) for b in range((K + 63) // 64)]
+    return entries, tiles

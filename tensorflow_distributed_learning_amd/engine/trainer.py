@@ -23,6 +23,7 @@ import torch
 
 from ..data import dataset as D
 from ..parallel import input_lib
+from .slab import transpose_tables
 from ..utils.tracing import trace_range
 
 
@@ -202,14 +203,8 @@ class GenericTrainer:
         # 4-D (conv) kernels also get an OHWI bf16 copy (the implicit-GEMM forward's weight rows),
         # refreshed with the cast by one transpose kernel over the whole slab
         if getattr(self, "_Wt", None) is None:
-            entries, tiles = [], []
-            for i, (spec, off) in enumerate(zip(layout.specs, layout.offsets)):
-                if len(spec.shape) != 4 or i >= len(self._leaves):
-                    continue
-                R, K = spec.shape[0] * spec.shape[1] * spec.shape[2], spec.shape[3]
-                e = len(entries)
-                entries.append([off, off, R, K])
-                tiles += [[e, a, b, 0] for a in range((R + 63) // 64) for b in range((K + 63) // 64)]
+            n = len(self._leaves)
+            entries, tiles = transpose_tables(layout.specs[:n], layout.offsets[:n])
             self._Wt = torch.empty_like(self._Wc) if entries else False
             if entries:
                 assert max(o + r * k for o, _, r, k in entries) <= self.W.numel()
