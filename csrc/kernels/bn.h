@@ -44,4 +44,28 @@ void bn_backward(const void* dy, const void* x, const void* y, void* dz, void* d
                  const float* shift, float* dgamma, float* dbeta, float* coef, int mode, int acc, hipStream_t s,
                  int given_parts = 0);  // > 0: dy is the masked dz and part holds its reduction
 
+// Synchronized (cross-replica) batch norm: the finalize of either direction split around an
+// all-reduce.  `*_pack` reduces this replica's partial rows (its own pass over the tensor, or
+// given_parts rows as above) and writes them into rank `rank`'s slot of the exchange buffer xbuf
+// (f32, xnumel >= bn_sync_xbuf_numel(C, R) elements, 16-byte aligned), zeroing the rest of it; the
+// caller SUM-all-reduces xbuf across the R replicas; `*_finalize` adds the replicas' sums in rank
+// order and finishes as bn_forward_stats / bn_backward do, with the global sums and row count.
+int64_t bn_sync_xbuf_numel(int C, int R);
+void bn_sync_forward_pack(const void* x, BnDType dt, int64_t M, int C, float* part, float* xbuf, int64_t xnumel,
+                          int rank, hipStream_t s, int given_parts = 0);
+void bn_sync_forward_finalize(const float* xbuf, int R, int C, const float* gamma, const float* beta,
+                              const float* mean_off, float* mean, float* invstd, float* scale, float* shift,
+                              float* moving_mean, float* moving_var, float momentum, float eps, hipStream_t s);
+// dgamma / dbeta: from this replica's LOCAL sums (the gradient all-reduce adds the replicas');
+// mode 2 without given_parts writes dz as bn_backward does
+void bn_sync_backward_pack(const void* dy, const void* x, const void* y, void* dz, BnDType dt, int64_t M, int C,
+                           float* part, const float* mean, const float* invstd, const float* scale,
+                           const float* shift, float* dgamma, float* dbeta, int mode, int acc, float* xbuf,
+                           int64_t xnumel, int rank, hipStream_t s, int given_parts = 0);
+// coef [3][C] from the global sums, then dx = A*dz + B*x + D over this replica's rows (mask: dz is
+// dy, masked by x*scale+shift > 0 as in mode 1)
+void bn_sync_backward_finalize(const float* xbuf, int R, const void* dz, const void* x, void* dx, BnDType dt, int64_t M,
+                               int C, const float* gamma, const float* mean, const float* invstd, const float* scale,
+                               const float* shift, float* coef, bool mask, hipStream_t s);
+
 }  // namespace tdl

@@ -649,4 +649,228 @@ void bn_backward(const void* dy, const void* x, const void* y, void* dz, void* d
                                   mode, acc, s, given_parts);
 }
 
+// ---- synchronized (cross-replica) statistics ------------------------------------------------------
+// The finalize of either direction split in two around an all-reduce of a small exchange buffer:
+//   pack     : this replica's partial rows -> (S, Q) per channel in f64 (reduce_parts), written as
+//              f32 hi/lo pairs into this rank's slot of xbuf; every other element of xbuf is zeroed,
+//              so a SUM all-reduce of xbuf is an exact all-gather in whatever order it adds
+//   finalize : every rank's (S, Q, M) rebuilt in f64 and added in rank order (the same bits on every
+//              replica), then the arithmetic of k_bn_fwd_finalize / k_bn_bwd_finalize on the totals
+// xbuf: [R] slots of [4][Cpad] f32 (S hi, S lo, Q hi, Q lo) + kSyncHdr header words (the slot's row
+// count as two 24-bit halves, exact in f32), Cpad = C rounded up to 4 (16-byte rows).
+namespace {
+
+constexpr int kSyncHdr = 4;
+
+__host__ __device__ inline int sync_cpad(int C) { return (C + 3) & ~3; }
+
+__device__ __forceinline__ void split_hi_lo(double v, float& hi, float& lo) {
+  hi = (float)v;
+  // a non-finite sum travels in hi alone (Inf - Inf would put a NaN beside an Inf)
+  lo = (hi - hi == 0.f) ? (float)(v - (double)hi) : 0.f;
+}
+
+// mean != nullptr (backward): also this replica's LOCAL dgamma / dbeta (the gradient all-reduce sums
+// them across replicas afterwards), from the local sums and the global mean / invstd
+__global__ __launch_bounds__(1024) void k_bn_sync_pack(const float* __restrict__ part, int P, int64_t M, int C,
+                                                      float* __restrict__ xbuf, int64_t xn, int rank,
+                                                      const float* __restrict__ mean,
+                                                      const float* __restrict__ invstd, float* __restrict__ dgamma,
+                                                      float* __restrict__ dbeta, int acc) {
+  const int Cp = sync_cpad(C);
+  const int64_t slot = 4 * (int64_t)Cp + kSyncHdr;
+  const int64_t own0 = rank * slot;
+  // zero everything this kernel does not write below: the other ranks' slots, the padding channels
+  // and unused header words of this one, and whatever lies behind the last slot
+  for (int64_t i = (int64_t)blockIdx.x * 1024 + threadIdx.x; i < xn; i += (int64_t)gridDim.x * 1024) {
+    const int64_t o = i - own0;
+    bool mine = false;
+    if (o >= 0 && o < 4 * (int64_t)Cp)
+      mine = (int)(o % Cp) < C;
+    else if (o >= 0 && o < slot)
+      mine = o - 4 * (int64_t)Cp < 2;
+    if (!mine) xbuf[i] = 0.f;
+  }
+  double S, Q;
+  if (!reduce_parts(part, P, C, S, Q)) return;
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  float* own = xbuf + own0;
+  split_hi_lo(S, own[c], own[Cp + c]);
+  split_hi_lo(Q, own[2 * Cp + c], own[3 * Cp + c]);
+  if (c == 0) {
+    own[4 * Cp] = (float)(M & 0xffffff);
+    own[4 * Cp + 1] = (float)(M >> 24);
+  }
+  if (mean != nullptr) {
+    const double mu = mean[c], inv = invstd[c];
+    const double dg = (Q - mu * S) * inv, db = S;
+    if (dgamma) dgamma[c] = (acc & 1) ? dgamma[c] + (float)dg : (float)dg;
+    if (dbeta) dbeta[c] = (acc & 2) ? dbeta[c] + (float)db : (float)db;
+  }
+}
+
+// totals of channel c over the R slots of an all-reduced xbuf, in rank order
+__device__ __forceinline__ void sync_totals(const float* __restrict__ xbuf, int R, int C, int c, double& S, double& Q,
+                                            double& M) {
+  const int Cp = sync_cpad(C);
+  const int64_t slot = 4 * (int64_t)Cp + kSyncHdr;
+  S = Q = M = 0.0;
+  for (int r = 0; r < R; ++r) {
+    const float* sl = xbuf + r * slot;
+    S += (double)sl[c] + (double)sl[Cp + c];
+    Q += (double)sl[2 * Cp + c] + (double)sl[3 * Cp + c];
+    M += (double)sl[4 * Cp] + (double)sl[4 * Cp + 1] * 16777216.0;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_bn_sync_fwd_finalize(const float* __restrict__ xbuf, int R, int C,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta,
+                                                            const float* __restrict__ mean_off,
+                                                            float* __restrict__ mean, float* __restrict__ invstd,
+                                                            float* __restrict__ scale, float* __restrict__ shift,
+                                                            float* __restrict__ mm, float* __restrict__ mv,
+                                                            float momentum, float eps) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  double S, Q, M;
+  sync_totals(xbuf, R, C, c, S, Q, M);
+  const double Md = M > 0.0 ? M : 1.0;  // (every replica's batch empty: no division by zero)
+  const double mu = S / Md;
+  const double var = fmax(Q / Md - mu * mu, 0.0);
+  const float inv = (float)(1.0 / sqrt(var + (double)eps));
+  const float g = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
+  mean[c] = (float)mu;
+  invstd[c] = inv;
+  scale[c] = g * inv;
+  shift[c] = be - (float)mu * g * inv;
+  if (mm != nullptr) {
+    const double unb = M > 1.0 ? var * M / (M - 1.0) : var;
+    const float mu_o = (float)mu + (mean_off ? mean_off[c] : 0.f);
+    mm[c] = mm[c] * momentum + mu_o * (1.f - momentum);
+    mv[c] = mv[c] * momentum + (float)unb * (1.f - momentum);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_bn_sync_bwd_finalize(const float* __restrict__ xbuf, int R, int C,
+                                                            const float* __restrict__ gamma,
+                                                            const float* __restrict__ mean,
+                                                            const float* __restrict__ invstd,
+                                                            float* __restrict__ coef) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  double S, Q, M;
+  sync_totals(xbuf, R, C, c, S, Q, M);
+  const double Md = M > 0.0 ? M : 1.0;
+  const double mu = mean[c], inv = invstd[c];
+  const double g = gamma ? gamma[c] : 1.0;
+  const double dg = (Q - mu * S) * inv, db = S;  // over the global batch
+  const double A = g * inv, B = -g * inv * inv * dg / Md;
+  coef[c] = (float)A;
+  coef[C + c] = (float)B;
+  coef[2 * C + c] = (float)(-A * db / Md - B * mu);
+}
+
+void sync_pack(float* part, int P, int64_t M, int C, float* xbuf, int64_t xnumel, int rank, const float* mean,
+               const float* invstd, float* dgamma, float* dbeta, int acc, hipStream_t s) {
+  const float* pr = prereduce(part, P, C, s);
+  hipLaunchKernelGGL(k_bn_sync_pack, dim3((C + 63) / 64), dim3(64 * kFinPhases), 0, s, pr, P, M, C, xbuf, xnumel, rank,
+                     mean, invstd, dgamma, dbeta, acc);
+}
+
+template <BnDType D>
+void sync_bwd_partial(const void* dy, const void* x, const void* y, void* dz, int64_t M, int C, float* part,
+                      const float* scale, const float* shift, int mode, const BnPlan& p, hipStream_t s) {
+  const dim3 gp(p.parts), blk(256);
+  if (mode == 0)
+    hipLaunchKernelGGL((k_bn_partial<D, 1>), gp, blk, 0, s, dy, x, nullptr, nullptr, nullptr, nullptr, M, C, p.rows_wg,
+                       part);
+  else if (mode == 1)
+    hipLaunchKernelGGL((k_bn_partial<D, 2>), gp, blk, 0, s, dy, x, nullptr, scale, shift, nullptr, M, C, p.rows_wg,
+                       part);
+  else
+    hipLaunchKernelGGL((k_bn_partial<D, 3>), gp, blk, 0, s, dy, x, y, nullptr, nullptr, dz, M, C, p.rows_wg, part);
+}
+
+template <BnDType D>
+void sync_dx(const void* dz, const void* x, void* dx, int64_t M, int C, const float* coef, const float* scale,
+             const float* shift, bool mask, hipStream_t s) {
+  const int64_t n8 = M * C / 8;
+  if (n8 == 0) return;
+  if (blocked_ok(D, C)) {
+    if (mask)
+      dx_blk<true>(dz, x, dx, n8, C, coef, scale, shift, s);
+    else
+      dx_blk<false>(dz, x, dx, n8, C, coef, nullptr, nullptr, s);
+    return;
+  }
+  const dim3 ge(elementwise_grid(n8)), blk(256);
+  const bool u2 = g_elem_unroll == 2 && D == BnDType::kBF16;
+  if (mask) {
+    if (u2)
+      hipLaunchKernelGGL((k_bn_dx<D, true, 2>), ge, blk, 0, s, dz, x, dx, n8, C, coef, scale, shift);
+    else
+      hipLaunchKernelGGL((k_bn_dx<D, true, 1>), ge, blk, 0, s, dz, x, dx, n8, C, coef, scale, shift);
+  } else {
+    if (u2)
+      hipLaunchKernelGGL((k_bn_dx<D, false, 2>), ge, blk, 0, s, dz, x, dx, n8, C, coef, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((k_bn_dx<D, false, 1>), ge, blk, 0, s, dz, x, dx, n8, C, coef, nullptr, nullptr);
+  }
+}
+
+}  // namespace
+
+int64_t bn_sync_xbuf_numel(int C, int R) { return (int64_t)R * (4 * (int64_t)sync_cpad(C) + kSyncHdr); }
+
+void bn_sync_forward_pack(const void* x, BnDType dt, int64_t M, int C, float* part, float* xbuf, int64_t xnumel,
+                          int rank, hipStream_t s, int given_parts) {
+  int P = given_parts;
+  if (given_parts <= 0) {
+    const BnPlan p = bn_plan(M, C);
+    if (dt == BnDType::kBF16)
+      hipLaunchKernelGGL((k_bn_partial<BnDType::kBF16, 0>), dim3(p.parts), dim3(256), 0, s, x, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, M, C, p.rows_wg, part);
+    else
+      hipLaunchKernelGGL((k_bn_partial<BnDType::kF32, 0>), dim3(p.parts), dim3(256), 0, s, x, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, M, C, p.rows_wg, part);
+    P = p.parts;
+  }
+  sync_pack(part, P, M, C, xbuf, xnumel, rank, nullptr, nullptr, nullptr, nullptr, 0, s);
+}
+
+void bn_sync_forward_finalize(const float* xbuf, int R, int C, const float* gamma, const float* beta,
+                              const float* mean_off, float* mean, float* invstd, float* scale, float* shift,
+                              float* moving_mean, float* moving_var, float momentum, float eps, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_sync_fwd_finalize, dim3((C + 63) / 64), dim3(64), 0, s, xbuf, R, C, gamma, beta, mean_off,
+                     mean, invstd, scale, shift, moving_mean, moving_var, momentum, eps);
+}
+
+void bn_sync_backward_pack(const void* dy, const void* x, const void* y, void* dz, BnDType dt, int64_t M, int C,
+                           float* part, const float* mean, const float* invstd, const float* scale,
+                           const float* shift, float* dgamma, float* dbeta, int mode, int acc, float* xbuf,
+                           int64_t xnumel, int rank, hipStream_t s, int given_parts) {
+  int P = given_parts;
+  if (given_parts <= 0) {
+    const BnPlan p = bn_plan(M, C);
+    if (dt == BnDType::kBF16)
+      sync_bwd_partial<BnDType::kBF16>(dy, x, y, dz, M, C, part, scale, shift, mode, p, s);
+    else
+      sync_bwd_partial<BnDType::kF32>(dy, x, y, dz, M, C, part, scale, shift, mode, p, s);
+    P = p.parts;
+  }
+  sync_pack(part, P, M, C, xbuf, xnumel, rank, mean, invstd, dgamma, dbeta, acc, s);
+}
+
+void bn_sync_backward_finalize(const float* xbuf, int R, const void* dz, const void* x, void* dx, BnDType dt, int64_t M,
+                               int C, const float* gamma, const float* mean, const float* invstd, const float* scale,
+                               const float* shift, float* coef, bool mask, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_sync_bwd_finalize, dim3((C + 63) / 64), dim3(64), 0, s, xbuf, R, C, gamma, mean, invstd,
+                     coef);
+  if (dt == BnDType::kBF16)
+    sync_dx<BnDType::kBF16>(dz, x, dx, M, C, coef, scale, shift, mask, s);
+  else
+    sync_dx<BnDType::kF32>(dz, x, dx, M, C, coef, scale, shift, mask, s);
+}
+
 }  // namespace tdl

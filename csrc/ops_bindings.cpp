@@ -201,6 +201,145 @@ at::Tensor bn_stats_train(at::Tensor x, c10::optional<at::Tensor> gamma, c10::op
                          part_in, false)[0];
 }
 
+// ---- synchronized batch norm (kernels/bn.h): pack -> [the caller's SUM all-reduce of xbuf] -> finalize
+static at::Tensor bn_sync_xbuf(const at::Tensor& x, int64_t C, int64_t rank, int64_t R, int64_t numel) {
+  TORCH_CHECK(R >= 1 && rank >= 0 && rank < R, "sync batch_norm: rank must be in [0, R)");
+  const int64_t need = tdl::bn_sync_xbuf_numel((int)C, (int)R);
+  TORCH_CHECK(numel == 0 || numel >= need, "sync batch_norm: exchange buffer of ", numel, " elements, ", need, " needed");
+  auto xbuf = fresh({numel > 0 ? numel : need}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(xbuf.data_ptr()) % 16 == 0, "sync batch_norm: 16-byte aligned exchange buffer");
+  return xbuf;
+}
+
+static void bn_sync_check_xbuf(const at::Tensor& xbuf, int64_t C, int64_t R) {
+  TORCH_CHECK(xbuf.is_cuda() && xbuf.is_contiguous() && xbuf.scalar_type() == at::kFloat && R >= 1 &&
+                  xbuf.numel() >= tdl::bn_sync_xbuf_numel((int)C, (int)R),
+              "sync batch_norm: xbuf must be the f32 exchange buffer of bn_sync_*_pack");
+}
+
+static at::Tensor bn_sync_part(const c10::optional<at::Tensor>& part_in, const at::Tensor& x, int64_t M, int64_t C,
+                               int& given) {
+  given = 0;
+  if (part_in.has_value() && part_in->defined()) {
+    given = parts_rows(*part_in, C);
+    return *part_in;
+  }
+  const tdl::BnPlan plan = tdl::bn_plan(M, (int)C);
+  return fresh({(int64_t)plan.part_rows * 2 * C}, x.options().dtype(at::kFloat));
+}
+
+// this replica's sums of x and x*x (its own pass, or part_in from a conv epilogue) into rank `rank`'s
+// slot of a fresh exchange buffer (numel > 0: that many elements, for a size no other collective uses)
+at::Tensor bn_sync_forward_pack(at::Tensor x, int64_t rank, int64_t R, c10::optional<at::Tensor> part_in,
+                                int64_t numel) {
+  bn_check(x);
+  const int64_t C = x.size(-1), M = x.numel() / C;
+  TORCH_CHECK(M > 0 && M < (int64_t(1) << 48), "sync batch_norm: row count out of range");
+  int given = 0;
+  at::Tensor part = bn_sync_part(part_in, x, M, C, given);
+  at::Tensor xbuf = bn_sync_xbuf(x, C, rank, R, numel);
+  tdl::bn_sync_forward_pack(x.data_ptr(), bn_dtype(x), M, (int)C, part.data_ptr<float>(), xbuf.data_ptr<float>(),
+                            xbuf.numel(), (int)rank, cur_stream(), given);
+  return xbuf;
+}
+
+// xbuf all-reduced: (y, stats[4][C]) or, apply = false, (stats) -- as bn_forward_train / bn_stats_train
+std::vector<at::Tensor> bn_sync_forward_finalize(at::Tensor x, at::Tensor xbuf, int64_t R,
+                                                 c10::optional<at::Tensor> gamma, c10::optional<at::Tensor> beta,
+                                                 c10::optional<at::Tensor> moving_mean,
+                                                 c10::optional<at::Tensor> moving_var, double momentum, double eps,
+                                                 bool relu, c10::optional<at::Tensor> residual,
+                                                 c10::optional<at::Tensor> mean_off, bool apply) {
+  bn_check(x);
+  const int64_t C = x.size(-1), M = x.numel() / C;
+  bn_sync_check_xbuf(xbuf, C, R);
+  const void* res = nullptr;
+  if (residual.has_value() && residual->defined()) {
+    bn_check(*residual);
+    TORCH_CHECK(residual->scalar_type() == x.scalar_type() && residual->numel() == x.numel(),
+                "batch_norm: residual must match x");
+    res = residual->data_ptr();
+  }
+  auto st = fresh({4, C}, x.options().dtype(at::kFloat));
+  float* mm = const_cast<float*>(opt_f32(moving_mean));
+  float* mv = const_cast<float*>(opt_f32(moving_var));
+  TORCH_CHECK((mm == nullptr) == (mv == nullptr), "batch_norm: moving mean and variance go together");
+  hipStream_t s = cur_stream();
+  float* sp = st.data_ptr<float>();
+  tdl::bn_sync_forward_finalize(xbuf.data_ptr<float>(), (int)R, (int)C, opt_f32(gamma), opt_f32(beta),
+                                opt_f32(mean_off), sp, sp + C, sp + 2 * C, sp + 3 * C, mm, mv, (float)momentum,
+                                (float)eps, s);
+  if (!apply) return {st};
+  auto y = fresh(x.sizes(), x.options());
+  tdl::bn_apply(x.data_ptr(), res, y.data_ptr(), bn_dtype(x), M, (int)C, sp + 2 * C, sp + 3 * C, relu ? 1 : 0, s);
+  return {y, st};
+}
+
+// returns (xbuf, dgamma, dbeta, dz): dgamma / dbeta from this replica's LOCAL sums (or added into
+// dgamma_out / dbeta_out); dz: what bn_sync_backward_finalize takes (mode 2: the masked gradient, also
+// the residual's; else dy)
+std::vector<at::Tensor> bn_sync_backward_pack(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> y, at::Tensor st,
+                                              int64_t mode, int64_t rank, int64_t R,
+                                              c10::optional<at::Tensor> dgamma_out,
+                                              c10::optional<at::Tensor> dbeta_out, c10::optional<at::Tensor> part_in,
+                                              int64_t numel) {
+  bn_check(x);
+  bn_check(dy);
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.numel() == x.numel(), "batch_norm backward: dy/x mismatch");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "batch_norm backward: bad mode");
+  const int64_t C = x.size(-1), M = x.numel() / C;
+  TORCH_CHECK(M > 0 && M < (int64_t(1) << 48), "sync batch_norm: row count out of range");
+  TORCH_CHECK(st.is_cuda() && st.is_contiguous() && st.numel() == 4 * C && st.scalar_type() == at::kFloat,
+              "batch_norm: stats [4][C]");
+  int given = 0;
+  at::Tensor part = bn_sync_part(part_in, x, M, C, given);
+  const void* yp = nullptr;
+  at::Tensor dz = dy;
+  if (mode == 2 && given == 0) {
+    TORCH_CHECK(y.has_value() && y->defined(), "batch_norm backward mode 2 needs y");
+    bn_check(*y);
+    TORCH_CHECK(y->scalar_type() == x.scalar_type() && y->numel() == x.numel(), "batch_norm backward: y/x mismatch");
+    yp = y->data_ptr();
+    dz = fresh(x.sizes(), x.options());
+  }
+  auto out = fresh({2, C}, x.options().dtype(at::kFloat));
+  auto check_out = [&](const c10::optional<at::Tensor>& t) {
+    if (!t.has_value() || !t->defined()) return (float*)nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->numel() == C,
+                "batch_norm backward: gradient outputs must be contiguous f32 [C]");
+    return t->data_ptr<float>();
+  };
+  float* pg = check_out(dgamma_out);
+  float* pb = check_out(dbeta_out);
+  const int acc = (pg ? 1 : 0) | (pb ? 2 : 0);
+  at::Tensor xbuf = bn_sync_xbuf(x, C, rank, R, numel);
+  float* o = out.data_ptr<float>();
+  const float* sp = st.data_ptr<float>();
+  tdl::bn_sync_backward_pack(dy.data_ptr(), x.data_ptr(), yp, yp ? dz.data_ptr() : nullptr, bn_dtype(x), M, (int)C,
+                             part.data_ptr<float>(), sp, sp + C, sp + 2 * C, sp + 3 * C, pg ? pg : o, pb ? pb : o + C,
+                             (int)mode, acc, xbuf.data_ptr<float>(), xbuf.numel(), (int)rank, cur_stream(), given);
+  return {xbuf, pg ? *dgamma_out : out[0], pb ? *dbeta_out : out[1], dz};
+}
+
+// xbuf all-reduced: dx over this replica's rows (mask: dz is the unmasked dy of a BN -> ReLU group)
+at::Tensor bn_sync_backward_finalize(at::Tensor dz, at::Tensor x, at::Tensor xbuf, int64_t R,
+                                     c10::optional<at::Tensor> gamma, at::Tensor st, bool mask) {
+  bn_check(x);
+  bn_check(dz);
+  TORCH_CHECK(dz.scalar_type() == x.scalar_type() && dz.numel() == x.numel(), "batch_norm backward: dz/x mismatch");
+  const int64_t C = x.size(-1), M = x.numel() / C;
+  bn_sync_check_xbuf(xbuf, C, R);
+  TORCH_CHECK(st.is_cuda() && st.is_contiguous() && st.numel() == 4 * C && st.scalar_type() == at::kFloat,
+              "batch_norm: stats [4][C]");
+  auto coef = fresh({3, C}, x.options().dtype(at::kFloat));
+  auto dx = fresh(x.sizes(), x.options());
+  const float* sp = st.data_ptr<float>();
+  tdl::bn_sync_backward_finalize(xbuf.data_ptr<float>(), (int)R, dz.data_ptr(), x.data_ptr(), dx.data_ptr(), bn_dtype(x),
+                                 M, (int)C, opt_f32(gamma), sp, sp + C, sp + 2 * C, sp + 3 * C, coef.data_ptr<float>(),
+                                 mask, cur_stream());
+  return dx;
+}
+
 static const float* bn_ss_of(const c10::optional<at::Tensor>& st, int64_t C) {
   if (!st.has_value() || !st->defined()) return nullptr;
   TORCH_CHECK(st->is_cuda() && st->is_contiguous() && st->scalar_type() == at::kFloat && st->numel() == 4 * C,
@@ -1092,4 +1231,25 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("y"), pybind11::arg("gamma"), pybind11::arg("stats"), pybind11::arg("mode"),
         pybind11::arg("dgamma_out") = pybind11::none(), pybind11::arg("dbeta_out") = pybind11::none(),
         pybind11::arg("part") = pybind11::none());
+  m.def("bn_sync_xbuf_numel", [](int64_t C, int64_t R) { return tdl::bn_sync_xbuf_numel((int)C, (int)R); },
+        "elements of the exchange buffer of a synchronized batch norm over C channels and R replicas");
+  m.def("bn_sync_forward_pack", &bn_sync_forward_pack, "synchronized batch norm: local sums -> exchange buffer",
+        pybind11::arg("x"), pybind11::arg("rank"), pybind11::arg("R"), pybind11::arg("part") = pybind11::none(),
+        pybind11::arg("numel") = 0);
+  m.def("bn_sync_forward_finalize", &bn_sync_forward_finalize,
+        "synchronized batch norm: all-reduced exchange buffer -> statistics (+ apply)", pybind11::arg("x"),
+        pybind11::arg("xbuf"), pybind11::arg("R"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("moving_mean"), pybind11::arg("moving_var"), pybind11::arg("momentum"), pybind11::arg("eps"),
+        pybind11::arg("relu") = false, pybind11::arg("residual") = pybind11::none(),
+        pybind11::arg("mean_off") = pybind11::none(), pybind11::arg("apply") = true);
+  m.def("bn_sync_backward_pack", &bn_sync_backward_pack,
+        "synchronized batch norm backward: local sums -> exchange buffer, local dgamma / dbeta", pybind11::arg("dy"),
+        pybind11::arg("x"), pybind11::arg("y"), pybind11::arg("stats"), pybind11::arg("mode"), pybind11::arg("rank"),
+        pybind11::arg("R"), pybind11::arg("dgamma_out") = pybind11::none(),
+        pybind11::arg("dbeta_out") = pybind11::none(), pybind11::arg("part") = pybind11::none(),
+        pybind11::arg("numel") = 0);
+  m.def("bn_sync_backward_finalize", &bn_sync_backward_finalize,
+        "synchronized batch norm backward: all-reduced exchange buffer -> dx", pybind11::arg("dz"), pybind11::arg("x"),
+        pybind11::arg("xbuf"), pybind11::arg("R"), pybind11::arg("gamma"), pybind11::arg("stats"),
+        pybind11::arg("mask") = false);
 }

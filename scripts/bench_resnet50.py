@@ -42,6 +42,8 @@ def main():
                     help="1: MIOpen find-mode solver search per conv shape (torch.backends.cudnn.benchmark)")
     ap.add_argument("--strategy", default="mirrored", choices=["mirrored", "mwms"],
                     help="mwms: MultiWorkerMirroredStrategy over TF_CONFIG workers (BASELINE config 5)")
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="BatchNormalization(synchronized=True): batch statistics over all replicas")
     args = ap.parse_args()
 
     if args.strategy == "mwms" and not os.environ.get("TF_CONFIG") and "WORLD_SIZE" not in os.environ:
@@ -86,7 +88,8 @@ def main():
 
     with strategy.scope():
         model = tdl.keras.applications.ResNet50(weights=None, classes=args.classes, classifier_activation=None,
-                                                input_shape=(args.image, args.image, 3))
+                                                input_shape=(args.image, args.image, 3),
+                                                **({"synchronized_batch_norm": True} if args.sync_bn else {}))
         model.compile(loss=tdl.keras.losses.SparseCategoricalCrossentropy(from_logits=True),
                       optimizer=tdl.keras.optimizers.SGD(learning_rate=0.01, momentum=0.9),
                       metrics=["sparse_categorical_accuracy"])
@@ -129,6 +132,12 @@ def main():
     from tensorflow_distributed_learning_amd.parallel import consistency
 
     identical = consistency.replicas_identical(comm, trainer.W)
+    sync_bn = None
+    if args.sync_bn:
+        n_sync = sum(1 for l in model.layers if getattr(l, "synchronized", False))
+        # one statistics exchange per layer and direction (none on a single replica)
+        sync_bn = {"layers": n_sync, "exchanges_per_step": 2 * n_sync if R > 1 else 0,
+                   "exchange_elements": list(getattr(trainer, "_sync_bn_sizes", []))}
     if strategy.extended.rank == 0:
         print(json.dumps({
             "metric": "images/sec (whole node) ResNet-50 synthetic ImageNet-shaped",
@@ -148,7 +157,8 @@ def main():
                                     "bytes": trainer.plan.bucket_bytes, "wire_dtype": trainer.plan.wire_dtype,
                                     "overlapped_with_backward": trainer._buckets is not None}
                                    if R > 1 and getattr(trainer, "plan", None) else None),
-                       "replicas_identical": identical, "final_loss": round(logs["loss"], 4)},
+                       "replicas_identical": identical, "final_loss": round(logs["loss"], 4),
+                       **({"sync_bn": sync_bn} if sync_bn is not None else {})},
         }), flush=True)
     if strategy.extended.rank == 0:
         from tensorflow_distributed_learning_amd.ops import conv as _conv

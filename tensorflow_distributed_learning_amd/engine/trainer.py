@@ -158,6 +158,7 @@ class GenericTrainer:
             self._Wc = torch.empty(self.W.numel(), dtype=torch.bfloat16, device=self.device)
             self._bind_compute_views()
         self._buckets = self._make_buckets()
+        self._prepare_sync_bn()
         self._bind_cast_accumulate()
         # whole-step hipGraphs (forward + backward + all-reduce + optimizer + metrics), keyed by
         # the batch signature; the first two steps of a signature run eagerly (solver search,
@@ -279,6 +280,37 @@ class GenericTrainer:
         self._counts = list(self._pending)
         self._register_bucket_hooks()
         return ranges
+
+    def _prepare_sync_bn(self):
+        """Synchronized BatchNormalization layers (ops/batchnorm.py) all-reduce a small exchange buffer on
+        the compute stream in their forward and backward: create the channels of those sizes now
+        (collective: every rank has the same layers), so that the whole-step graph records them on the
+        xGMI kernel.  Channels are keyed by element count and a gradient bucket may be in flight on the
+        side stream meanwhile, so the exchange sizes step past every bucket's."""
+        comm = self.comm
+        self._sync_bn_sizes = []
+        if comm.world_size == 1 or self.device.type != "cuda" or getattr(comm, "threaded", False):
+            return
+        from ..keras import layers as L
+        from ..ops import batchnorm as _bn
+
+        def walk(m):
+            for l in getattr(m, "layers", []):
+                yield l
+                yield from walk(l)
+
+        chans = sorted({int(l.moving_mean.shape[0]) for l in walk(self.model)
+                        if isinstance(l, L.BatchNormalization) and l.synchronized and l.trainable and l.built})
+        chans = [c for c in chans if c % 8 == 0 and c <= 2048]  # (what the kernels take)
+        if not chans:
+            return
+        xg = getattr(comm, "xgmi", None)
+        avoid = set()
+        for s, e in (self._buckets or []):  # (a bucket above the channel limit goes in chunk-sized pieces)
+            avoid.update([e - s] if xg is None else [c for _, c in xg._chunks(e - s)])
+        comm._bn_sync_avoid = avoid
+        self._sync_bn_sizes = [_bn.sync_exchange_numel(comm, c) for c in chans]
+        comm.prepare_all_reduce(*self._sync_bn_sizes)
 
     def _register_bucket_hooks(self):
         """Post-accumulate hooks on the CURRENT leaves: the last gradient of a bucket launches that

@@ -19,7 +19,9 @@ list; the plan rewrites, at execution time only (the layer graph, variables, che
   operand loaders apply relu(x * scale + shift) to the BN input; the normalised tensor is never written.
 * ``BatchNormalization -> ReLU -> [ZeroPadding2D ->] MaxPooling2D('valid')`` (the ResNet stem): the pool
   runs on the BN input with the normalisation in its kernel and reduces the BN backward sums in its
-  backward pass; the normalised tensor is never written.
+  backward pass; the normalised tensor is never written.  Not for a ``synchronized`` layer: its
+  statistics come from every replica through ``batch_norm_train(sync=...)``, which this group bypasses
+  (all the other groups go through it and work synchronized, conv-epilogue statistics included).
 * ``ZeroPadding2D -> Conv2D`` with <= 4 input channels, 'valid', column stride 2 (the ResNet stem):
   the padding goes into the stem kernel's packed image (ops/conv.py ``stem_conv2d_nhwc``).
 * a tensor read by a Conv2D and by one other node (the ResNet block input: the shortcut / the
@@ -195,6 +197,10 @@ def _plan_bn_pool(p: Plan, only_consumer):
     for key, g in list(p.groups.items()):
         if not g.relu or g.residual is not None or g.conv_reader:
             continue
+        if getattr(g.bn_node.layer, "synchronized", False):
+            # the pool kernel takes the statistics from its own finalize, past batch_norm_train: a
+            # synchronized layer (statistics over all replicas) keeps its BN -> ReLU group instead
+            continue
         c = only_consumer(g.out)
         pool_n, pads, pad_zero = None, ((0, 0), (0, 0)), False
         if c is not None and isinstance(c.layer, L.ZeroPadding2D):
@@ -299,7 +305,8 @@ def run_group(g: Group, vals, training, taps=None, boxes=None):
             y = batch_norm_train(x, bn.gamma.value if bn.gamma is not None else None,
                                  bn.beta.value if bn.beta is not None else None, bn.moving_mean.value,
                                  bn.moving_variance.value, bn.momentum, bn.epsilon, relu=True, conv_bias=cb,
-                                 grad_out=bn._grad_targets(), part=getattr(x, "_tdl_bn_part", None))
+                                 grad_out=bn._grad_targets(), part=getattr(x, "_tdl_bn_part", None),
+                                 sync=bn._sync_comm(training))
             y = pool_layer(y, training=training, **({"_zero_pad": pads} if pad_zero else {}))
         vals[id(g.out)] = y
         return
@@ -309,7 +316,7 @@ def run_group(g: Group, vals, training, taps=None, boxes=None):
                          bn.beta.value if bn.beta is not None else None, bn.moving_mean.value,
                          bn.moving_variance.value, bn.momentum, bn.epsilon, relu=g.relu, residual=r, conv_bias=cb,
                          grad_out=bn._grad_targets(), part=getattr(x, "_tdl_bn_part", None), stats_out=st,
-                         defer_apply=defer)
+                         defer_apply=defer, sync=bn._sync_comm(training))
     if defer:  # y is a stand-in: the reading 1x1 conv applies relu(bn(x)) in its operand loaders
         y._tdl_bn_in = st[0]
     if g.relu and (r is not None or g.conv_reader) and y.is_cuda:

@@ -717,7 +717,10 @@ class ZeroPadding2D(Layer):
 
 class BatchNormalization(Layer):
     """Keras BatchNormalization: per-replica batch statistics (not synchronised, the Keras default);
-    moving mean/variance are ON_READ variables averaged across replicas when read."""
+    moving mean/variance are ON_READ variables averaged across replicas when read.
+    ``synchronized=True``: the training statistics (and the backward's gradient sums) are taken over
+    the global batch of all replicas of the strategy the layer was created under, so the result does
+    not depend on how the batch is cut; the moving statistics then come out identical everywhere."""
 
     def __init__(self, axis=-1, momentum=0.99, epsilon=1e-3, center=True, scale=True, beta_initializer="zeros",
                  gamma_initializer="ones", moving_mean_initializer="zeros", moving_variance_initializer="ones",
@@ -730,7 +733,21 @@ class BatchNormalization(Layer):
         self.gamma_initializer = _init.get(gamma_initializer)
         self.mm_init = _init.get(moving_mean_initializer)
         self.mv_init = _init.get(moving_variance_initializer)
-        self.synchronized = synchronized
+        self.synchronized = bool(synchronized)
+        # synchronized: the strategy whose replicas share the batch statistics -- the one this layer is
+        # created under (a replica thread of a single-process MirroredStrategy gets its replica's view)
+        from ..parallel.strategy import get_strategy, has_strategy
+
+        self._sync_strategy = get_strategy() if (self.synchronized and has_strategy()) else None
+
+    def _sync_comm(self, training):
+        """The communicator a synchronized layer's training statistics are reduced over, else None."""
+        if not (self.synchronized and training and self.trainable):
+            return None
+        from ..parallel.strategy import get_strategy
+
+        comm = (self._sync_strategy or get_strategy()).extended.communicator
+        return comm if comm.world_size > 1 else None
 
     def build(self, input_shape):
         c = int(input_shape[self.axis])
@@ -746,6 +763,18 @@ class BatchNormalization(Layer):
 
     def call(self, x, training=None):
         axis = self.axis % x.dim()
+        comm = self._sync_comm(training)
+        if comm is not None:
+            # statistics over the global batch (ops/batchnorm.py: the HIP kernels where they apply,
+            # else PyTorch ops with float64 sums through the same communicator)
+            from ..ops import batchnorm as _bn
+
+            h = x if axis == x.dim() - 1 else x.movedim(axis, -1)
+            y = _bn.batch_norm_train(h, self.gamma.value if self.gamma is not None else None,
+                                     self.beta.value if self.beta is not None else None, self.moving_mean.value,
+                                     self.moving_variance.value, self.momentum, self.epsilon,
+                                     grad_out=self._grad_targets() if _bn.supported(h) else None, sync=comm)
+            return y if axis == x.dim() - 1 else y.movedim(-1, axis)
         if training and self.trainable and axis == x.dim() - 1 and x.is_cuda:
             # NHWC training on the GPU: hand-written batch-norm kernels (ops/batchnorm.py)
             from ..ops import batchnorm as _bn
@@ -784,8 +813,29 @@ class BatchNormalization(Layer):
         return s
 
     def get_config(self):
-        return dict(super().get_config(), axis=self.axis, momentum=self.momentum, epsilon=self.epsilon,
-                    center=self.center, scale=self.scale)
+        cfg = dict(super().get_config(), axis=self.axis, momentum=self.momentum, epsilon=self.epsilon,
+                   center=self.center, scale=self.scale)
+        if self.synchronized:  # (only when set: configs of plain layers are what they always were)
+            cfg["synchronized"] = True
+        return cfg
+
+
+class SyncBatchNormalization(BatchNormalization):
+    """tf.keras.layers.experimental.SyncBatchNormalization: ``BatchNormalization(synchronized=True)`` --
+    training statistics over the global batch of all replicas."""
+
+    def __init__(self, *args, **kw):
+        kw["synchronized"] = True
+        super().__init__(*args, **kw)
+
+
+class _Experimental:
+    """``keras.layers.experimental``"""
+
+    SyncBatchNormalization = SyncBatchNormalization
+
+
+experimental = _Experimental()
 
 
 class LayerNormalization(Layer):
@@ -902,5 +952,5 @@ def multiply(inputs, **kw):
 
 LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
-    Reshape, Activation, ReLU, Softmax, Dropout, Rescaling, ZeroPadding2D, BatchNormalization, LayerNormalization,
-    Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    Reshape, Activation, ReLU, Softmax, Dropout, Rescaling, ZeroPadding2D, BatchNormalization, SyncBatchNormalization,
+    LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}

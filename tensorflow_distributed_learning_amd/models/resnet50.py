@@ -11,50 +11,55 @@ from __future__ import annotations
 from typing import Optional
 
 
-def _block(x, filters, L, stride=1, conv_shortcut=True, name=""):
+def _block(x, filters, L, stride=1, conv_shortcut=True, name="", bn_kw=None):
     bn_eps = 1.001e-5
+    bn_kw = bn_kw or {}
     if conv_shortcut:
         sc = L.Conv2D(4 * filters, 1, strides=stride, name=name + "_0_conv")(x)
-        sc = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_0_bn")(sc)
+        sc = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_0_bn", **bn_kw)(sc)
     else:
         sc = x
     x = L.Conv2D(filters, 1, strides=stride, name=name + "_1_conv")(x)
-    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_1_bn")(x)
+    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_1_bn", **bn_kw)(x)
     x = L.Activation("relu", name=name + "_1_relu")(x)
     x = L.Conv2D(filters, 3, padding="same", name=name + "_2_conv")(x)
-    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_2_bn")(x)
+    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_2_bn", **bn_kw)(x)
     x = L.Activation("relu", name=name + "_2_relu")(x)
     x = L.Conv2D(4 * filters, 1, name=name + "_3_conv")(x)
-    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_3_bn")(x)
+    x = L.BatchNormalization(axis=3, epsilon=bn_eps, name=name + "_3_bn", **bn_kw)(x)
     x = L.Add(name=name + "_add")([sc, x])
     return L.Activation("relu", name=name + "_out")(x)
 
 
-def _stack(x, filters, blocks, L, stride1=2, name=""):
-    x = _block(x, filters, L, stride=stride1, name=name + "_block1")
+def _stack(x, filters, blocks, L, stride1=2, name="", bn_kw=None):
+    x = _block(x, filters, L, stride=stride1, name=name + "_block1", bn_kw=bn_kw)
     for i in range(2, blocks + 1):
-        x = _block(x, filters, L, conv_shortcut=False, name=name + "_block" + str(i))
+        x = _block(x, filters, L, conv_shortcut=False, name=name + "_block" + str(i), bn_kw=bn_kw)
     return x
 
 
 def ResNet50(include_top: bool = True, weights=None, input_tensor=None, input_shape=None, pooling=None,  # noqa: N802
-             classes: int = 1000, classifier_activation: Optional[str] = "softmax", keras_module=None, **kw):
+             classes: int = 1000, classifier_activation: Optional[str] = "softmax", keras_module=None,
+             synchronized_batch_norm: bool = False, **kw):
+    """``synchronized_batch_norm``: every BatchNormalization with ``synchronized=True`` (training statistics
+    over the global batch of all replicas; not a tf.keras.applications argument)."""
     if weights not in (None, "none"):
         raise ValueError("pretrained weights are not available offline; use weights=None")
     if keras_module is None:
         from .. import keras as keras_module
     L = keras_module.layers
+    bn_kw = {"synchronized": True} if synchronized_batch_norm else {}
     inp = input_tensor if input_tensor is not None else L.Input(shape=input_shape or (224, 224, 3), name="input_1")
     x = L.ZeroPadding2D(padding=((3, 3), (3, 3)), name="conv1_pad")(inp)
     x = L.Conv2D(64, 7, strides=2, name="conv1_conv")(x)
-    x = L.BatchNormalization(axis=3, epsilon=1.001e-5, name="conv1_bn")(x)
+    x = L.BatchNormalization(axis=3, epsilon=1.001e-5, name="conv1_bn", **bn_kw)(x)
     x = L.Activation("relu", name="conv1_relu")(x)
     x = L.ZeroPadding2D(padding=((1, 1), (1, 1)), name="pool1_pad")(x)
     x = L.MaxPooling2D(3, strides=2, name="pool1_pool")(x)
-    x = _stack(x, 64, 3, L, stride1=1, name="conv2")
-    x = _stack(x, 128, 4, L, name="conv3")
-    x = _stack(x, 256, 6, L, name="conv4")
-    x = _stack(x, 512, 3, L, name="conv5")
+    x = _stack(x, 64, 3, L, stride1=1, name="conv2", bn_kw=bn_kw)
+    x = _stack(x, 128, 4, L, name="conv3", bn_kw=bn_kw)
+    x = _stack(x, 256, 6, L, name="conv4", bn_kw=bn_kw)
+    x = _stack(x, 512, 3, L, name="conv5", bn_kw=bn_kw)
     if include_top:
         x = L.GlobalAveragePooling2D(name="avg_pool")(x)
         x = L.Dense(classes, activation=classifier_activation, name="predictions")(x)

@@ -199,6 +199,12 @@ class SyncOnReadVariable(Variable):
 
         if not in_cross_replica_context():
             return self._value
+        comm = s.extended.communicator
+        if getattr(comm, "threaded", False) and comm._solo():
+            # single-process multi-device strategy read from the user's thread (get_weights before the
+            # replica models are cloned, or after fit): only this replica's copy exists here -- as for
+            # a broadcast there (parallel/local_replicas.py) -- so the read is its value
+            return self._value
         op = "MEAN" if self.aggregation == VariableAggregation.MEAN else "SUM"
         if self.aggregation == VariableAggregation.ONLY_FIRST_REPLICA:
             t = self._value.clone()
