@@ -5,6 +5,12 @@
 //           max pool) or zero (a fused ZeroPadding2D in front, the ResNet stem).
 // backward: gather form — each input element sums dy over the <= ceil(k/s)^2 windows whose
 //           argmax points at it: no atomics, deterministic, one pass over dx.
+// NaN     : the compare is `v > best`, which is false for a NaN, so a NaN input never wins a window: the
+//           output is the maximum of the window's other elements (-inf, argmax 255, when all of them are
+//           NaN and the padding is -inf), unlike torch.max_pool2d, which propagates it.  Argmax bytes stay in
+//           {0 .. kh*kw-1, 255}, every element of dx is written, and a NaN element gets no gradient.
+//           For the same reason a real -inf input never beats the initial -inf: a window of nothing but
+//           -inf (and NaN) gives y = -inf with argmax 255, and its gradient is dropped.
 #include <cstdlib>
 
 #include "common.h"
@@ -15,10 +21,14 @@ namespace {
 
 __device__ __forceinline__ float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-__device__ __forceinline__ uint32_t f2bf(float f) {
-  uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return u >> 16;
+// v[0..8) rounded to the bf16 values a store would write (round to nearest even, a NaN stays a NaN)
+__device__ __forceinline__ void round_bf16x8(float* v) {
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) {
+    const uint32_t u = pack_bf16x2(v[j], v[j + 1]);
+    v[j] = bf_lo(u);
+    v[j + 1] = bf_hi(u);
+  }
 }
 
 template <bool BF>
@@ -38,10 +48,10 @@ template <bool BF>
 __device__ __forceinline__ void st8(void* p, int64_t e, const float* v) {
   if (BF) {
     uint4 u;
-    u.x = f2bf(v[0]) | (f2bf(v[1]) << 16);
-    u.y = f2bf(v[2]) | (f2bf(v[3]) << 16);
-    u.z = f2bf(v[4]) | (f2bf(v[5]) << 16);
-    u.w = f2bf(v[6]) | (f2bf(v[7]) << 16);
+    u.x = pack_bf16x2(v[0], v[1]);
+    u.y = pack_bf16x2(v[2], v[3]);
+    u.z = pack_bf16x2(v[4], v[5]);
+    u.w = pack_bf16x2(v[6], v[7]);
     *reinterpret_cast<uint4*>(static_cast<uint16_t*>(p) + e) = u;
   } else {
     f4* q = reinterpret_cast<f4*>(static_cast<float*>(p) + e);
@@ -58,10 +68,8 @@ __device__ __forceinline__ void st8(void* p, int64_t e, const float* v) {
 template <bool BF>
 __device__ __forceinline__ void bn_relu8(float* v, const float* sc, const float* sh) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float o = fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f);
-    v[j] = BF ? __uint_as_float(f2bf(o) << 16) : o;  // the value the BN pass would have stored
-  }
+  for (int j = 0; j < 8; ++j) v[j] = fmaxf(fmaf(v[j], sc[j], sh[j]), 0.f);
+  if (BF) round_bf16x8(v);  // the value the BN pass would have stored
 }
 
 template <bool BF, bool K3S2, bool BNF = false>
@@ -233,10 +241,10 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd(const void* __restrict__ dy
         }
       }
     if constexpr (BNF) {
+      if (BF) round_bf16x8(acc);  // the stored dz is the bf16 value; the sums are over exactly what is stored
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        // the stored dz is the bf16 value; the sums are over exactly what is stored
-        const float d = fmaf(xv[j], msc[j], msh[j]) > 0.f ? (BF ? __uint_as_float(f2bf(acc[j]) << 16) : acc[j]) : 0.f;
+        const float d = fmaf(xv[j], msc[j], msh[j]) > 0.f ? acc[j] : 0.f;
         acc[j] = d;
         bs[j] += d;
         bq[j] = fmaf(d, xv[j], bq[j]);

@@ -60,8 +60,14 @@ tdl::BnDType bn_dtype(const at::Tensor& x) {
 void bn_check(const at::Tensor& x) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 2, "batch_norm: contiguous [..., C] GPU tensor expected");
   const int64_t C = x.size(-1);
-  TORCH_CHECK(C % 8 == 0 && C <= 2048, "batch_norm: C must be a multiple of 8 and <= 2048");
+  TORCH_CHECK(C >= 8 && C % 8 == 0 && C <= 2048, "batch_norm: C must be a multiple of 8, at least 8 and <= 2048");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "batch_norm: 16-byte aligned data expected");
+}
+
+// the BN kernels divide by the row count: an empty batch is refused here (ops/batchnorm.py sends it to PyTorch)
+void bn_check_rows(const at::Tensor& x) {
+  bn_check(x);
+  TORCH_CHECK(x.numel() > 0, "batch_norm: empty batch (no rows)");
 }
 
 const float* opt_f32(const c10::optional<at::Tensor>& t) {
@@ -90,7 +96,7 @@ static std::vector<at::Tensor> bn_forward_impl(at::Tensor x, c10::optional<at::T
                                                bool relu, c10::optional<at::Tensor> residual,
                                                c10::optional<at::Tensor> mean_off, c10::optional<at::Tensor> part_in,
                                                bool apply) {
-  bn_check(x);
+  bn_check_rows(x);
   const int64_t C = x.size(-1), M = x.numel() / C;
   const void* res = nullptr;
   if (residual.has_value() && residual->defined()) {
@@ -135,17 +141,19 @@ std::vector<at::Tensor> bn_backward(at::Tensor dy, at::Tensor x, c10::optional<a
                                     c10::optional<at::Tensor> gamma, at::Tensor st, int64_t mode,
                                     c10::optional<at::Tensor> dgamma_out, c10::optional<at::Tensor> dbeta_out,
                                     c10::optional<at::Tensor> part_in) {
-  bn_check(x);
+  bn_check_rows(x);
   bn_check(dy);
   TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.numel() == x.numel(), "batch_norm backward: dy/x mismatch");
   TORCH_CHECK(mode >= 0 && mode <= 2, "batch_norm backward: bad mode");
   const int64_t C = x.size(-1), M = x.numel() / C;
-  TORCH_CHECK(st.is_contiguous() && st.numel() == 4 * C && st.scalar_type() == at::kFloat, "batch_norm: stats [4][C]");
+  TORCH_CHECK(st.is_cuda() && st.is_contiguous() && st.numel() == 4 * C && st.scalar_type() == at::kFloat,
+              "batch_norm: stats [4][C]");
   const void* yp = nullptr;
   at::Tensor dz;
   if (mode == 2 && !(part_in.has_value() && part_in->defined())) {
     TORCH_CHECK(y.has_value() && y->defined(), "batch_norm backward mode 2 needs y");
     bn_check(*y);
+    TORCH_CHECK(y->scalar_type() == x.scalar_type() && y->numel() == x.numel(), "batch_norm backward: y/x mismatch");
     yp = y->data_ptr();
     dz = fresh(x.sizes(), x.options());
   } else if (mode == 2) {
@@ -232,7 +240,7 @@ static at::Tensor bn_sync_part(const c10::optional<at::Tensor>& part_in, const a
 // slot of a fresh exchange buffer (numel > 0: that many elements, for a size no other collective uses)
 at::Tensor bn_sync_forward_pack(at::Tensor x, int64_t rank, int64_t R, c10::optional<at::Tensor> part_in,
                                 int64_t numel) {
-  bn_check(x);
+  bn_check_rows(x);
   const int64_t C = x.size(-1), M = x.numel() / C;
   TORCH_CHECK(M > 0 && M < (int64_t(1) << 48), "sync batch_norm: row count out of range");
   int given = 0;
@@ -250,7 +258,7 @@ std::vector<at::Tensor> bn_sync_forward_finalize(at::Tensor x, at::Tensor xbuf, 
                                                  c10::optional<at::Tensor> moving_var, double momentum, double eps,
                                                  bool relu, c10::optional<at::Tensor> residual,
                                                  c10::optional<at::Tensor> mean_off, bool apply) {
-  bn_check(x);
+  bn_check_rows(x);
   const int64_t C = x.size(-1), M = x.numel() / C;
   bn_sync_check_xbuf(xbuf, C, R);
   const void* res = nullptr;
@@ -283,7 +291,7 @@ std::vector<at::Tensor> bn_sync_backward_pack(at::Tensor dy, at::Tensor x, c10::
                                               c10::optional<at::Tensor> dgamma_out,
                                               c10::optional<at::Tensor> dbeta_out, c10::optional<at::Tensor> part_in,
                                               int64_t numel) {
-  bn_check(x);
+  bn_check_rows(x);
   bn_check(dy);
   TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.numel() == x.numel(), "batch_norm backward: dy/x mismatch");
   TORCH_CHECK(mode >= 0 && mode <= 2, "batch_norm backward: bad mode");
@@ -324,7 +332,7 @@ std::vector<at::Tensor> bn_sync_backward_pack(at::Tensor dy, at::Tensor x, c10::
 // xbuf all-reduced: dx over this replica's rows (mask: dz is the unmasked dy of a BN -> ReLU group)
 at::Tensor bn_sync_backward_finalize(at::Tensor dz, at::Tensor x, at::Tensor xbuf, int64_t R,
                                      c10::optional<at::Tensor> gamma, at::Tensor st, bool mask) {
-  bn_check(x);
+  bn_check_rows(x);
   bn_check(dz);
   TORCH_CHECK(dz.scalar_type() == x.scalar_type() && dz.numel() == x.numel(), "batch_norm backward: dz/x mismatch");
   const int64_t C = x.size(-1), M = x.numel() / C;
@@ -359,6 +367,8 @@ std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t kh, int64_t kw, int64_
                   (int)kh, (int)kw, (int)sh, (int)sw, (int)pt, (int)pl, pad_zero ? 1 : 0};
   auto y = fresh({x.size(0), OH, OW, x.size(3)}, x.options());
   auto arg = fresh({x.size(0), OH, OW, x.size(3)}, x.options().dtype(at::kByte));
+  if (bn_stats.has_value() && bn_stats->defined()) bn_ss_of(bn_stats, x.size(3));
+  if (y.numel() == 0) return {y, arg};  // an empty batch: nothing to launch
   tdl::maxpool_forward(x.data_ptr(), y.data_ptr(), arg.data_ptr<uint8_t>(), bn_dtype(x) == tdl::BnDType::kBF16, g,
                        cur_stream(), bn_ss_of(bn_stats, x.size(3)));
   return {y, arg};
@@ -373,6 +383,7 @@ at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor arg, std::vector<int64_t> in_sh
   tdl::PoolGeom g{(int)in_shape[0], (int)in_shape[1], (int)in_shape[2], (int)in_shape[3], (int)dy.size(1),
                   (int)dy.size(2), (int)kh, (int)kw, (int)sh, (int)sw, (int)pt, (int)pl, 0};
   auto dx = fresh(in_shape, dy.options());
+  if (dx.numel() == 0) return dx;  // an empty batch: nothing to launch
   tdl::maxpool_backward(dy.data_ptr(), arg.data_ptr<uint8_t>(), dx.data_ptr(), bn_dtype(dy) == tdl::BnDType::kBF16, g,
                         cur_stream());
   return dx;
@@ -397,6 +408,8 @@ std::vector<at::Tensor> maxpool_bwd_bn(at::Tensor dy, at::Tensor arg, std::vecto
   auto dx = fresh(in_shape, dy.options());
   const int64_t P = tdl::maxpool_backward_blocks(g);
   auto part = fresh({P + (P + 63) / 64, 2, C}, dy.options().dtype(at::kFloat));
+  bn_ss_of(bn_stats, C);
+  if (dx.numel() == 0) return {dx, part};  // an empty batch: nothing to launch (and no partial rows)
   tdl::maxpool_backward(dy.data_ptr(), arg.data_ptr<uint8_t>(), dx.data_ptr(), bn_dtype(dy) == tdl::BnDType::kBF16, g,
                         cur_stream(), bn_x.data_ptr(), bn_ss_of(bn_stats, C), part.data_ptr<float>());
   return {dx, part};
@@ -1157,7 +1170,16 @@ void register_ops(pybind11::module& m) {
   m.def("gap_fwd", &gap_fwd, "NHWC bf16 global average pooling");
   m.def("gap_bwd", &gap_bwd, "NHWC bf16 global average pooling backward");
   m.def("slab_cast_bf16", &slab_cast_bf16, "f32 -> bf16 copy of a whole weight slab (one launch)");
-  m.def("bn_set_tuning", &tdl::bn_set_tuning, "BN kernel sweep hooks (max_parts, elem_blocks, elem_unroll; 0 = keep)");
+  m.def("bn_set_tuning", &tdl::bn_set_tuning,
+        "BN kernel sweep hooks (max_parts, elem_blocks: grid cap of the grid-stride elementwise kernels, elem_unroll, "
+        "blk_blocks: grid cap of the blocked elementwise kernels; 0 = keep)",
+        pybind11::arg("max_parts"), pybind11::arg("elem_blocks"), pybind11::arg("elem_unroll"),
+        pybind11::arg("blk_blocks") = 0);
+  m.def("bn_get_tuning", [] {
+    int v[4];
+    tdl::bn_get_tuning(v);
+    return std::make_tuple(v[0], v[1], v[2], v[3]);
+  }, "(max_parts, elem_blocks, elem_unroll, blk_blocks) as bn_set_tuning set them");
   m.def("bn_set_elementwise", &tdl::bn_set_elementwise,
         "BN elementwise kernel family A/B hook (kind 0 grid-stride / 1 blocked, vectors per thread 2/4/8)");
   m.def("slab_transpose_bf16", &slab_transpose_bf16, "HWIO f32 conv kernels -> OHWI bf16, all in one launch");

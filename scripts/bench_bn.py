@@ -43,7 +43,7 @@ def main():
         tc = t(lambda: y.copy_(x))
         rec = {"shape": [M, Ch], "copy_TBps": round(2 * nb / tc / 1e6, 2)}
         for cfg in CONFIGS:
-            C.bn_set_tuning(*cfg[:3])
+            C.bn_set_tuning(*cfg[:3], cfg[1])  # (the same grid cap for either kernel family)
             C.bn_set_elementwise(*cfg[3:])
             yf, st = C.bn_forward_train(x, g, b, mm, mv, 0.99, 1e-3, True, None, None)
             t_f = t(lambda: C.bn_forward_train(x, g, b, mm, mv, 0.99, 1e-3, True, None, None))
@@ -58,9 +58,8 @@ def main():
             tot[key] = tot.get(key, 0.0) + t_f + t_fr + t_b1 + t_b2
         print(json.dumps(rec), flush=True)
     print(json.dumps({"total_us_per_config": {k: round(v, 1) for k, v in tot.items()}}))
-    C.bn_set_tuning(512, 4096, 1)  # the defaults (the blocked kernels' grid cap back to 8192 below)
+    C.bn_set_tuning(512, 4096, 1, 8192)  # the defaults
     C.bn_set_elementwise(1, 4)
-    C.bn_set_tuning(0, 8192, 0)
 
 
 if __name__ == "__main__":

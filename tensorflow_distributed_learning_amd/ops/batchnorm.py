@@ -34,8 +34,10 @@ FUSED_BWD_MODES = {0: 0, 1: 0, 2: 0}  # the same, by mode (0 plain, 1 relu, 2 ad
 
 
 def supported(x: torch.Tensor) -> bool:
-    C = x.shape[-1]
-    return x.is_cuda and x.dim() >= 2 and C % 8 == 0 and C <= 2048 and x.dtype in (torch.float32, torch.bfloat16)
+    # an empty batch (or C == 0) has no statistics for the kernels to divide by: PyTorch's semantics apply
+    C = x.shape[-1] if x.dim() >= 2 else 0
+    return x.is_cuda and x.dim() >= 2 and x.numel() > 0 and C % 8 == 0 and C <= 2048 and \
+        x.dtype in (torch.float32, torch.bfloat16)
 
 
 def _aligned(t: torch.Tensor) -> torch.Tensor:

@@ -14,7 +14,7 @@ from . import hip
 
 
 def supported(x: torch.Tensor) -> bool:
-    return x.is_cuda and x.dim() == 4 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048 and \
+    return x.is_cuda and x.dim() == 4 and x.numel() > 0 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048 and \
         x.dtype in (torch.float32, torch.bfloat16)
 
 
