@@ -269,27 +269,75 @@ class MnistStep {
   tdl::MnistArgs a_;
 };
 
-void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad) {
+// The clip operands of an update kernel (keras/optimizers.py): gscale = the [scale, norm] buffer that
+// clip_norm wrote (the kernel reads word 0), clipvalue = the clamp bound; both optional.
+using OptTensor = c10::optional<at::Tensor>;
+using OptDouble = c10::optional<double>;
+
+const float* gscale_ptr(const OptTensor& gscale) {
+  if (!gscale.has_value()) return nullptr;
+  check_slab_f32(*gscale, "gscale");
+  TORCH_CHECK(gscale->numel() >= 1, "gscale must hold the scale word");
+  return gscale->data_ptr<float>();
+}
+
+void set_clip(tdl::OptimArgs& a, const OptTensor& gscale, const OptDouble& clipvalue) {
+  a.gscale = gscale_ptr(gscale);
+  a.clip = clipvalue.has_value() ? 1 : 0;
+  a.clipvalue = clipvalue.has_value() ? (float)*clipvalue : 0.f;
+}
+
+// Global gradient norm of a flat f32 slab and the clip scale (csrc/kernels/clip.hip, two launches):
+// out[0] = scale = min(1, clipnorm / (norm + 1e-12)), out[1] = norm = |clamp(g, +-clipvalue)|_2 (f32 words;
+// the sum in f64, in an order that depends on g.numel() alone).  partials: f64 scratch of
+// >= clip_partials(g.numel()) elements.  An empty g launches no partial sums and writes norm 0, scale 1.
+void clip_norm_chunk(at::Tensor g, at::Tensor partials, at::Tensor out, double clipnorm, OptDouble clipvalue,
+                     int64_t chunk) {
+  check_slab_f32(g, "g");
+  check_slab_f32(out, "out");
+  TORCH_CHECK(partials.is_cuda() && partials.is_contiguous() && partials.scalar_type() == at::kDouble,
+              "partials must be a contiguous float64 GPU tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(partials.data_ptr()) % 16 == 0, "partials must be 16-byte aligned");
+  TORCH_CHECK(out.numel() >= 2, "out must hold [scale, norm]");
+  TORCH_CHECK(chunk == 2048 || chunk == 4096 || chunk == tdl::kClipChunk || chunk == 16384, "unknown chunk size");
+  TORCH_CHECK(partials.numel() >= tdl::clip_partials_count(g.numel(), chunk), "partials too small: ",
+              partials.numel(), " < ", tdl::clip_partials_count(g.numel(), chunk));
+  tdl::clip_norm_apply(g.data_ptr<float>(), partials.data_ptr<double>(), out.data_ptr<float>(), g.numel(),
+                       (float)clipnorm, clipvalue.has_value(), clipvalue.has_value() ? (float)*clipvalue : 0.f,
+                       cur_stream(), (int)chunk);
+}
+
+void clip_norm(at::Tensor g, at::Tensor partials, at::Tensor out, double clipnorm, OptDouble clipvalue) {
+  clip_norm_chunk(g, partials, out, clipnorm, clipvalue, tdl::kClipChunk);
+}
+
+void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad, OptTensor gscale, OptDouble clipvalue) {
   check_slab_f32(w, "w");
   check_slab_f32(g, "g");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel());
-  tdl::sgd_apply(w.data_ptr<float>(), g.data_ptr<float>(), lr.data_ptr<float>(), w.numel(), cur_stream(), zero_grad);
+  const float cv = clipvalue.has_value() ? (float)*clipvalue : 0.f;
+  tdl::sgd_apply(w.data_ptr<float>(), g.data_ptr<float>(), lr.data_ptr<float>(), w.numel(), cur_stream(), zero_grad,
+                 gscale_ptr(gscale), clipvalue.has_value() ? &cv : nullptr);
 }
 
-void sgd_momentum(at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor lr, double m, bool nesterov, bool zero_grad) {
+void sgd_momentum(at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor lr, double m, bool nesterov, bool zero_grad,
+                  OptTensor gscale, OptDouble clipvalue) {
   check_slab_f32(w, "w");
   check_slab_f32(g, "g");
   check_slab_f32(v, "v");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel() && v.numel() == w.numel());
+  const float cv = clipvalue.has_value() ? (float)*clipvalue : 0.f;
   tdl::sgd_momentum_apply(w.data_ptr<float>(), g.data_ptr<float>(), v.data_ptr<float>(), lr.data_ptr<float>(),
-                          (float)m, nesterov, w.numel(), cur_stream(), zero_grad);
+                          (float)m, nesterov, w.numel(), cur_stream(), zero_grad, gscale_ptr(gscale),
+                          clipvalue.has_value() ? &cv : nullptr);
 }
 
 // Flat-slab Adam / AdamW (+AMSGrad): state m, v (vhat), device lr and execution-start step t0
 void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<at::Tensor> vhat, at::Tensor lr,
-          at::Tensor t0, int64_t t_add, double b1, double b2, double eps, double wd) {
+          at::Tensor t0, int64_t t_add, double b1, double b2, double eps, double wd, OptTensor gscale,
+          OptDouble clipvalue) {
   for (auto* t : {&w, &g, &m, &v}) check_slab_f32(*t, "adam operand");
   for (auto* t : {&lr, &t0}) check_cuda_f32(*t, "adam operand");
   TORCH_CHECK(g.numel() == w.numel() && m.numel() == w.numel() && v.numel() == w.numel());
@@ -303,12 +351,13 @@ void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<
   }
   a.lr = lr.data_ptr<float>(); a.t0 = t0.data_ptr<float>(); a.t_add = (int)t_add; a.n = w.numel();
   a.b1 = (float)b1; a.b2 = (float)b2; a.eps = (float)eps; a.wd = (float)wd;
+  set_clip(a, gscale, clipvalue);
   tdl::adam_apply(a, cur_stream());
 }
 
 // Flat-slab RMSprop (+momentum, centered)
 void rmsprop(at::Tensor w, at::Tensor g, at::Tensor rms, c10::optional<at::Tensor> mom, c10::optional<at::Tensor> mg,
-             at::Tensor lr, double rho, double momentum, double eps) {
+             at::Tensor lr, double rho, double momentum, double eps, OptTensor gscale, OptDouble clipvalue) {
   for (auto* t : {&w, &g, &rms}) check_slab_f32(*t, "rmsprop operand");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && rms.numel() == w.numel());
@@ -317,17 +366,20 @@ void rmsprop(at::Tensor w, at::Tensor g, at::Tensor rms, c10::optional<at::Tenso
   if (mom.has_value()) { check_slab_f32(*mom, "mom"); TORCH_CHECK(mom->numel() == w.numel()); a.s1 = mom->data_ptr<float>(); a.flags |= 1; }
   if (mg.has_value()) { check_slab_f32(*mg, "mg"); TORCH_CHECK(mg->numel() == w.numel()); a.s2 = mg->data_ptr<float>(); a.flags |= 2; }
   a.lr = lr.data_ptr<float>(); a.n = w.numel(); a.b1 = (float)rho; a.b2 = (float)momentum; a.eps = (float)eps;
+  set_clip(a, gscale, clipvalue);
   tdl::rmsprop_apply(a, cur_stream());
 }
 
 // Flat-slab Adagrad
-void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double eps) {
+void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double eps, OptTensor gscale,
+             OptDouble clipvalue) {
   for (auto* t : {&w, &g, &acc}) check_slab_f32(*t, "adagrad operand");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && acc.numel() == w.numel());
   tdl::OptimArgs a{};
   a.w = w.data_ptr<float>(); a.g = g.data_ptr<float>(); a.s0 = acc.data_ptr<float>();
   a.lr = lr.data_ptr<float>(); a.n = w.numel(); a.eps = (float)eps;
+  set_clip(a, gscale, clipvalue);
   tdl::adagrad_apply(a, cur_stream());
 }
 
@@ -366,17 +418,34 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("error", &MnistStep::error, pybind11::arg("reset") = false)
       .def("buffers", &MnistStep::buffers)
       .def("set_stamps", &MnistStep::set_stamps);
+  const auto none = pybind11::none();
+  m.attr("CLIP_CHUNK") = (int64_t)tdl::kClipChunk;           // elements per k_clip_partials workgroup
+  m.attr("CLIP_SCALE_THREADS") = (int64_t)tdl::kClipScaleThreads;  // threads of k_clip_scale
+  m.def("clip_partials", [](int64_t n) { return tdl::clip_partials_count(n); },
+        "f64 partial sums clip_norm needs for an n-element slab");
+  m.def("clip_norm", &clip_norm,
+        "out[0] = min(1, clipnorm / (|clamp(g)|_2 + 1e-12)), out[1] = the norm; deterministic f64 sum",
+        pybind11::arg("g"), pybind11::arg("partials"), pybind11::arg("out"), pybind11::arg("clipnorm"),
+        pybind11::arg("clipvalue") = none);
+  m.def("clip_norm_chunk", &clip_norm_chunk, "clip_norm at another chunk size (measurement only)",
+        pybind11::arg("g"), pybind11::arg("partials"), pybind11::arg("out"), pybind11::arg("clipnorm"),
+        pybind11::arg("clipvalue"), pybind11::arg("chunk"));
   m.def("sgd", &sgd, "w -= lr * g over a flat slab (zero_grad: g := 0 afterwards)", pybind11::arg("w"),
-        pybind11::arg("g"), pybind11::arg("lr"), pybind11::arg("zero_grad") = false);
+        pybind11::arg("g"), pybind11::arg("lr"), pybind11::arg("zero_grad") = false,
+        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
   m.def("sgd_momentum", &sgd_momentum, "Keras momentum SGD over a flat slab (zero_grad: g := 0 afterwards)",
         pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("v"), pybind11::arg("lr"), pybind11::arg("m"),
-        pybind11::arg("nesterov"), pybind11::arg("zero_grad") = false);
+        pybind11::arg("nesterov"), pybind11::arg("zero_grad") = false, pybind11::arg("gscale") = none,
+        pybind11::arg("clipvalue") = none);
   m.def("adam", &adam, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("m"), pybind11::arg("v"),
         pybind11::arg("vhat"), pybind11::arg("lr"), pybind11::arg("t0"), pybind11::arg("t_add"), pybind11::arg("b1"),
-        pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd") = 0.0);
+        pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd") = 0.0, pybind11::arg("gscale") = none,
+        pybind11::arg("clipvalue") = none);
   m.def("rmsprop", &rmsprop, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("rms"), pybind11::arg("mom"),
-        pybind11::arg("mg"), pybind11::arg("lr"), pybind11::arg("rho"), pybind11::arg("momentum"), pybind11::arg("eps"));
-  m.def("adagrad", &adagrad);
+        pybind11::arg("mg"), pybind11::arg("lr"), pybind11::arg("rho"), pybind11::arg("momentum"), pybind11::arg("eps"),
+        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+  m.def("adagrad", &adagrad, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("acc"), pybind11::arg("lr"),
+        pybind11::arg("eps"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
   register_ops(m);
   register_comm(m);
   register_rccl(m);

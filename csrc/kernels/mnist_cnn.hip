@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "mnist_cnn.h"
+#include "optim.h"
 #include "xgmi_device.h"
 
 namespace tdl {
@@ -1665,32 +1666,39 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
 // gz (optional, = g): the gradient is zeroed after its use, so the next step's backward can accumulate
 // into it without a separate fill launch (engine/trainer.py)
 // (g is not __restrict__: gz aliases it)
+// CLIP: g' = clamp(g, +-clipvalue) * *gscale where g is loaded (GradClip, optim.h); the unclipped
+// instantiations contain none of it
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ w, const float* g, const float* __restrict__ lrp,
-                                             int64_t n, float* gz) {
+                                             int64_t n, float* gz, const float* gscale, float clipvalue, int clip) {
+  const GradClip gc(CLIP ? gscale : nullptr, clipvalue, CLIP ? clip : 0);
   const float lr = *lrp;
   const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     f4 wv = ld4(w + i4);
-    const f4 gv = ld4(g + i4);
+    const f4 gv = grad_of<CLIP>(gc, ld4(g + i4));
     wv -= lr * gv;
     st4(w + i4, wv);
     if (gz != nullptr) st4(gz + i4, zero4());
   } else {
     for (int64_t j = i4; j < n; ++j) {
-      w[j] -= lr * g[j];
+      w[j] -= lr * grad_of<CLIP>(gc, g[j]);
       if (gz != nullptr) gz[j] = 0.f;
     }
   }
 }
 
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ w, const float* g,
                                                       float* __restrict__ v, const float* __restrict__ lrp,
-                                                      float m, int nesterov, int64_t n, float* gz) {
+                                                      float m, int nesterov, int64_t n, float* gz,
+                                                      const float* gscale, float clipvalue, int clip) {
+  const GradClip gc(CLIP ? gscale : nullptr, clipvalue, CLIP ? clip : 0);
   const float lr = *lrp;
   const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     f4 wv = ld4(w + i4), vv = ld4(v + i4);
-    const f4 gv = ld4(g + i4);
+    const f4 gv = grad_of<CLIP>(gc, ld4(g + i4));
     vv = m * vv - lr * gv;
     wv += nesterov ? (m * vv - lr * gv) : vv;
     st4(w + i4, wv);
@@ -1698,7 +1706,7 @@ __global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ w, con
     if (gz != nullptr) st4(gz + i4, zero4());
   } else {
     for (int64_t j = i4; j < n; ++j) {
-      const float gj = g[j];
+      const float gj = grad_of<CLIP>(gc, g[j]);
       const float vj = m * v[j] - lr * gj;
       v[j] = vj;
       w[j] += nesterov ? (m * vj - lr * gj) : vj;
@@ -1763,18 +1771,32 @@ void mnist_finalize_x(const MnistArgs& a, bool apply_sgd, hipStream_t s) {
     default: go(std::integral_constant<int, 1>{}); break;
   }
 }
-void sgd_apply(float* w, const float* g, const float* lr, int64_t n, hipStream_t s, bool zero_g) {
+void sgd_apply(float* w, const float* g, const float* lr, int64_t n, hipStream_t s, bool zero_g,
+               const float* gscale, const float* clipvalue) {
   if (n <= 0) return;
-  const int64_t nt = (n + 3) / 4;
-  hipLaunchKernelGGL(k_sgd, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w, g, lr, n,
-                     zero_g ? const_cast<float*>(g) : nullptr);
+  const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
+  float* gz = zero_g ? const_cast<float*>(g) : nullptr;
+  const float cv = clipvalue != nullptr ? *clipvalue : 0.f;
+  const int clip = clipvalue != nullptr;
+  if (gscale != nullptr || clip)
+    hipLaunchKernelGGL(k_sgd<true>, grid, dim3(256), 0, s, w, g, lr, n, gz, gscale, cv, clip);
+  else
+    hipLaunchKernelGGL(k_sgd<false>, grid, dim3(256), 0, s, w, g, lr, n, gz, gscale, cv, clip);
 }
 void sgd_momentum_apply(float* w, const float* g, float* v, const float* lr, float momentum, bool nesterov,
-                        int64_t n, hipStream_t s, bool zero_g) {
+                        int64_t n, hipStream_t s, bool zero_g, const float* gscale, const float* clipvalue) {
   if (n <= 0) return;
-  const int64_t nt = (n + 3) / 4;
-  hipLaunchKernelGGL(k_sgd_momentum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, w, g, v, lr, momentum,
-                     nesterov ? 1 : 0, n, zero_g ? const_cast<float*>(g) : nullptr);
+  const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
+  float* gz = zero_g ? const_cast<float*>(g) : nullptr;
+  const float cv = clipvalue != nullptr ? *clipvalue : 0.f;
+  const int clip = clipvalue != nullptr;
+  const int nest = nesterov ? 1 : 0;
+  if (gscale != nullptr || clip)
+    hipLaunchKernelGGL(k_sgd_momentum<true>, grid, dim3(256), 0, s, w, g, v, lr, momentum, nest, n, gz, gscale, cv,
+                       clip);
+  else
+    hipLaunchKernelGGL(k_sgd_momentum<false>, grid, dim3(256), 0, s, w, g, v, lr, momentum, nest, n, gz, gscale, cv,
+                       clip);
 }
 
 }  // namespace tdl

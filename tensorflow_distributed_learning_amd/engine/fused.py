@@ -89,8 +89,8 @@ def eligible(model, dataset=None) -> Optional[str]:
     opt = model.optimizer
     if type(opt) not in (optimizers.SGD, optimizers.Adam, optimizers.AdamW, optimizers.RMSprop, optimizers.Adagrad):
         return f"optimizer {type(opt).__name__} has no fused update"
-    if opt.clipnorm or opt.clipvalue or opt.global_clipnorm:
-        return "gradient clipping (a global norm) is not fused"
+    if opt._clipped and not hasattr(ops.hip(), "clip_norm"):
+        return "the extension has no clip_norm kernel (rebuild: python build_native.py)"
     if opt.weight_decay and not isinstance(opt, optimizers.Adam):
         return "decoupled weight decay is fused for Adam/AdamW only"
     kern = {"Adam": "adam", "AdamW": "adam", "RMSprop": "rmsprop", "Adagrad": "adagrad"}.get(type(opt).__name__)
@@ -215,10 +215,11 @@ class FusedMnistTrainer:
         """finalize + (all-reduce) + optimizer for one step (step ``k`` of its execution).  R > 1
         with plain SGD: one all-reduce of the whole 900 KB slab with the SGD update fused into it
         (xGMI kernel), when the communicator has one.  Other optimizers: finalize leaves the
-        gradient in G, their flat-slab kernel (csrc/kernels/optim.hip) applies it."""
+        gradient in G, their flat-slab kernel (csrc/kernels/optim.hip) applies it.  A clipped
+        optimizer is never plain: finalize(False) -> all-reduce -> clip_norm -> update kernel."""
         opt = self.optimizer
         self._step_k = k
-        plain = getattr(opt, "momentum", None) == 0 and type(opt).__name__ == "SGD"
+        plain = self._plain_sgd
         if self.R == 1 and plain:
             st.finalize(True, keep_grad=False)  # (nothing reads G on this path)
             return
@@ -380,8 +381,10 @@ class FusedMnistTrainer:
 
     @property
     def _plain_sgd(self) -> bool:
+        # (gradient clipping needs the whole reduced gradient before any update: never the SGD inside
+        # finalize, all_reduce_sgd, the exchange-in-finalize channel or the two-bucket overlap)
         opt = self.optimizer
-        return type(opt).__name__ == "SGD" and opt.momentum == 0
+        return type(opt).__name__ == "SGD" and opt.momentum == 0 and not opt._clipped
 
     def _update(self, lo: int = 0, hi: Optional[int] = None):
         from .. import ops
@@ -395,10 +398,11 @@ class FusedMnistTrainer:
             if not opt.device_update(W, G, getattr(self, "_step_k", 0)):
                 raise RuntimeError(f"fused trainer: {type(opt).__name__} has no device update on {W.device}")
             return
+        clip = opt.device_clip(G)  # (a clipped optimizer updates the whole slab: see _plain_sgd)
         if opt.momentum == 0:
-            C.sgd(W, G, opt.lr_dev)
+            C.sgd(W, G, opt.lr_dev, **clip)
         else:
-            C.sgd_momentum(W, G, opt._slots["momentum"][lo:hi], opt.lr_dev, opt.momentum, opt.nesterov)
+            C.sgd_momentum(W, G, opt._slots["momentum"][lo:hi], opt.lr_dev, opt.momentum, opt.nesterov, **clip)
 
     def _reduce_and_update(self):
         if self.R > 1:

@@ -272,7 +272,11 @@ class Model(Layer):
             comm.broadcast(W, 0)
             if NT is not None:
                 comm.broadcast(NT, 0)
-        self._W, self._G, self._NT, self._nt_layout = W, torch.zeros_like(W), NT, ntl
+        G = torch.zeros_like(W)
+        # the alignment padding between the variables is zero in G and no kernel writes it, so a norm
+        # over the whole slab (gradient clipping, csrc/kernels/clip.hip) is the norm of the variables
+        assert not bool(G.any()), "a fresh gradient slab must be all zero"
+        self._W, self._G, self._NT, self._nt_layout = W, G, NT, ntl
         self._slab_vars_sig = sig
         self._trainer = None
 

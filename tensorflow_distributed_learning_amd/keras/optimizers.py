@@ -5,7 +5,15 @@ all-reduce (TF applies ``ResourceApplyGradientDescent`` once per variable).  On 
 optimizer is one hand-written gfx950 kernel over the slab (``_C.sgd`` / ``_C.sgd_momentum``,
 ``_C.adam`` (AdamW's decay in the same pass), ``_C.rmsprop``, ``_C.adagrad``; csrc/kernels/optim.hip),
 with the learning rate and Adam's step count read from device memory so the update can sit inside
-a captured hipGraph.  Gradient clipping keeps its torch ops (a global norm).
+a captured hipGraph.
+
+Gradient clipping (``clipvalue``, ``clipnorm`` / ``global_clipnorm``) runs on the device too: two
+launches (``_C.clip_norm``, csrc/kernels/clip.hip) leave the global norm and the clip scale in device
+memory -- an f64 sum in an order fixed by the slab size, bit-identical on every run and replica --
+and the update kernel applies ``clamp(g, +-clipvalue) * scale`` where it loads ``g``: no extra pass
+over the gradient, no torch reduction, capturable.  The torch formulas (``_clip`` + ``_update``)
+remain the CPU implementation.  Their f32 sum of squares overflows to inf for a gradient norm above
+~1.8e19, where the device path's f64 sum still returns the finite norm.
 """
 from __future__ import annotations
 
@@ -34,6 +42,10 @@ class Optimizer:
         # correction on the device: a captured step graph reads it, each step adds its offset)
         self.t_dev: Optional[torch.Tensor] = None
         self._t_synced = None
+        # device clipping (build() on a GPU): [scale, norm, -, -] f32 written by _C.clip_norm and its
+        # f64 partial sums; allocated before any graph capture
+        self._clip_out: Optional[torch.Tensor] = None
+        self._clip_partials: Optional[torch.Tensor] = None
         unknown = set(kwargs) - {"decay", "amsgrad_legacy", "jit_compile", "is_legacy_optimizer",
                                  "use_ema", "ema_momentum", "ema_overwrite_frequency"}
         if unknown:
@@ -90,6 +102,12 @@ class Optimizer:
         self._lr_synced = (self.current_lr(), self.lr_dev.data_ptr())
         self.t_dev = torch.full((1,), float(self.iterations), dtype=torch.float32, device=device)
         self._t_synced = (float(self.iterations), self.t_dev.data_ptr())
+        self._clip_out = self._clip_partials = None
+        if self._clipped and device.type == "cuda" and _kernel_present("clip_norm"):
+            from .. import ops
+
+            self._clip_out = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
+            self._clip_partials = torch.zeros(max(1, ops.hip().clip_partials(n)), dtype=torch.float64, device=device)
         for k in self._slot_names():
             old = self._slots.get(k)
             self._slots[k] = old.to(device) if (old is not None and old.numel() == n) else torch.zeros(
@@ -102,10 +120,41 @@ class Optimizer:
         return self._slots
 
     # ------------------------------------------------------------------ update
+    def _clip_norm_value(self):
+        # (one norm over the whole slab for both options; Keras clips ``clipnorm`` per variable)
+        return self.global_clipnorm or self.clipnorm
+
+    @property
+    def _clipped(self) -> bool:
+        return self.clipvalue is not None or self._clip_norm_value() is not None
+
+    @property
+    def _clip_on_device(self) -> bool:
+        """Unclipped, or built on a GPU slab with the clip kernels: the device update applies the clip."""
+        return not self._clipped or self._clip_out is not None
+
+    @property
+    def last_clip_norm(self) -> Optional[torch.Tensor]:
+        """The gradient norm of the last device norm clip (a 1-element device view; None on the CPU)."""
+        return None if self._clip_out is None else self._clip_out[1:2]
+
+    def device_clip(self, G: torch.Tensor) -> dict:
+        """The clip operands of this optimizer's update kernel for the gradient slab ``G``; with a norm
+        clip, first the two ``clip_norm`` launches that write the scale.  Clamp, then the norm of the
+        clamped gradient, then the scale: the order of ``_clip``."""
+        if not self._clipped:
+            return {}
+        norm = self._clip_norm_value()
+        if norm is not None:
+            from .. import ops
+
+            ops.hip().clip_norm(G, self._clip_partials, self._clip_out, float(norm), self.clipvalue)
+        return {"gscale": self._clip_out if norm is not None else None, "clipvalue": self.clipvalue}
+
     def _clip(self, G: torch.Tensor):
         if self.clipvalue is not None:
             G.clamp_(-self.clipvalue, self.clipvalue)
-        norm = self.global_clipnorm or self.clipnorm
+        norm = self._clip_norm_value()
         if norm is not None:
             n = torch.linalg.vector_norm(G)
             G.mul_(torch.clamp(norm / (n + 1e-12), max=1.0))
@@ -117,6 +166,9 @@ class Optimizer:
             self.build(W.numel(), W.device)
         if sync_lr:
             self._sync_lr()
+        if self.device_update(W, G, t_add):  # clip + (decay +) update in the kernel
+            self.iterations += 1
+            return
         self._clip(G)
         if self.weight_decay:
             W.mul_(1.0 - self.current_lr() * self.weight_decay)
@@ -211,12 +263,15 @@ def _kernel_present(kernel: str) -> bool:
     return ops.hip_available() and hasattr(ops.hip(), kernel)
 
 
-def _hip_ok(t: torch.Tensor, kernel: str = "sgd") -> bool:
+def _hip_ok(t: torch.Tensor, kernel: str = "sgd", opt: Optional[Optimizer] = None) -> bool:
+    """``kernel`` can update the slab ``t`` (and apply ``opt``'s gradient clipping, if it has any)."""
     if t.device.type != "cuda" or t.dtype != torch.float32:
         return False
     from .. import ops
 
-    return hasattr(ops.hip(), kernel)  # ops.hip() raises loudly if the HIP kernels are missing on a GPU box
+    if not hasattr(ops.hip(), kernel):  # ops.hip() raises loudly if the HIP kernels are missing on a GPU box
+        return False
+    return opt is None or (opt._clip_on_device and (not opt._clipped or t.numel() == opt._n))
 
 
 class SGD(Optimizer):
@@ -236,17 +291,19 @@ class SGD(Optimizer):
         return ["momentum"] if self.momentum > 0 else []
 
     def device_update(self, W, G, t_add=0):
-        if not _hip_ok(W) or self.weight_decay:
+        if not _hip_ok(W, "sgd", self) or self.weight_decay:
             return False
         from .. import ops
 
         C = ops.hip()
+        clip = self.device_clip(G)
         # (the generic trainer's request: zero G after its use, so its next step needs no fill launch)
         zero = bool(getattr(self, "_zero_grad_after", False))
         if self.momentum > 0:
-            C.sgd_momentum(W, G, self._slots["momentum"], self.lr_dev, self.momentum, self.nesterov, zero_grad=zero)
+            C.sgd_momentum(W, G, self._slots["momentum"], self.lr_dev, self.momentum, self.nesterov, zero_grad=zero,
+                           **clip)
         else:
-            C.sgd(W, G, self.lr_dev, zero_grad=zero)
+            C.sgd(W, G, self.lr_dev, zero_grad=zero, **clip)
         self._zeroed_grad = zero
         return True
 
@@ -279,34 +336,23 @@ class Adam(Optimizer):
     @property
     def graph_safe(self) -> bool:
         """Whether a captured step replays this update correctly: only the kernel path reads the
-        learning rate and the step count from device memory (t_dev); the clipping fallback
-        (_update) bakes the capture-time values into the graph."""
-        if self.clipvalue is not None or self.clipnorm or self.global_clipnorm:
-            return False
-        return _kernel_present("adam")
+        learning rate and the step count from device memory (t_dev); the torch fallback (_update)
+        bakes the capture-time values into the graph.  A clipped optimizer takes the kernel path once
+        it is built on a GPU slab (build() allocates the clip buffers there)."""
+        return self._clip_on_device and _kernel_present("adam")
 
     _needs_step = True
 
     def device_update(self, W, G, t_add=0):
         """csrc/kernels/optim.hip k_adam (AdamW's decoupled decay inside the same pass)."""
-        if not _hip_ok(W, "adam"):
+        if not _hip_ok(W, "adam", self):
             return False
         from .. import ops
 
         ops.hip().adam(W, G, self._slots["m"], self._slots["v"], self._slots.get("vhat"), self.lr_dev, self.t_dev,
-                       int(t_add), self.beta_1, self.beta_2, self.epsilon, float(self.weight_decay or 0.0))
+                       int(t_add), self.beta_1, self.beta_2, self.epsilon, float(self.weight_decay or 0.0),
+                       **self.device_clip(G))
         return True
-
-    def apply_flat(self, W, G, sync_lr: bool = True, t_add: int = 0):
-        if self._n != W.numel() or self._device != W.device:
-            self.build(W.numel(), W.device)
-        if sync_lr:
-            self._sync_lr()
-        if (self.clipvalue is None and not (self.global_clipnorm or self.clipnorm)
-                and self.device_update(W, G, t_add)):  # decay + update in one kernel
-            self.iterations += 1
-            return
-        super().apply_flat(W, G, sync_lr=False)
 
     def _update(self, W, G):
         t = self.iterations + 1
@@ -340,16 +386,17 @@ class RMSprop(Optimizer):
     def _slot_names(self):
         return ["rms"] + (["mom"] if self.momentum > 0 else []) + (["mg"] if self.centered else [])
 
-    graph_safe = property(lambda self: _kernel_present("rmsprop"))  # (the torch fallback bakes lr)
+    # (the torch fallback bakes lr; clipping: see Adam.graph_safe)
+    graph_safe = property(lambda self: self._clip_on_device and _kernel_present("rmsprop"))
 
     def device_update(self, W, G, t_add=0):
         """csrc/kernels/optim.hip k_rmsprop."""
-        if not _hip_ok(W, "rmsprop") or self.weight_decay:
+        if not _hip_ok(W, "rmsprop", self) or self.weight_decay:
             return False
         from .. import ops
 
         ops.hip().rmsprop(W, G, self._slots["rms"], self._slots.get("mom"), self._slots.get("mg"), self.lr_dev,
-                          self.rho, self.momentum, self.epsilon)
+                          self.rho, self.momentum, self.epsilon, **self.device_clip(G))
         return True
 
     def _update(self, W, G):
@@ -386,15 +433,15 @@ class Adagrad(Optimizer):
         if fresh:
             self._slots["acc"].fill_(self.init_acc)
 
-    graph_safe = property(lambda self: _kernel_present("adagrad"))
+    graph_safe = property(lambda self: self._clip_on_device and _kernel_present("adagrad"))
 
     def device_update(self, W, G, t_add=0):
         """csrc/kernels/optim.hip k_adagrad."""
-        if not _hip_ok(W, "adagrad") or self.weight_decay:
+        if not _hip_ok(W, "adagrad", self) or self.weight_decay:
             return False
         from .. import ops
 
-        ops.hip().adagrad(W, G, self._slots["acc"], self.lr_dev, self.epsilon)
+        ops.hip().adagrad(W, G, self._slots["acc"], self.lr_dev, self.epsilon, **self.device_clip(G))
         return True
 
     def _update(self, W, G):
