@@ -6,6 +6,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPStream.h>
 
+#include <cmath>
 #include <vector>
 
 #include "kernels/mnist_cnn.h"
@@ -383,6 +384,202 @@ void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double e
   tdl::adagrad_apply(a, cur_stream());
 }
 
+// Layer tables of the layer-wise optimizers (csrc/kernels/layerwise.hip, optim.h): the only source of the
+// indices those kernels use, validated here on the host.  The launchers accept nothing else.
+struct LayerTables {
+  at::Tensor chunks, first_chunk, wd, adapt;
+  int64_t V = 0, C = 0, n = 0, chunk = tdl::kLayerChunk;
+};
+
+// chunk: kLayerChunk, or one of the measured candidates 4096 / 8192 (scripts/bench_layerwise.py)
+LayerTables layer_tables_chunk(std::vector<int64_t> offsets, std::vector<int64_t> sizes, int64_t n,
+                               std::vector<double> wd, std::vector<bool> adapt, int64_t chunk) {
+  TORCH_CHECK(chunk == tdl::kLayerChunk || chunk == 4096 || chunk == 8192, "unknown chunk size");
+  const size_t V = offsets.size();
+  TORCH_CHECK(sizes.size() == V && wd.size() == V && adapt.size() == V,
+              "layer_tables: offsets, sizes, wd and adapt must have one entry per variable");
+  TORCH_CHECK(n >= 0 && n < (int64_t(1) << 31), "layer_tables: slab size ", n, " out of the int32 range");
+  std::vector<int32_t> chunks, first;
+  int64_t end = 0;
+  for (size_t i = 0; i < V; ++i) {
+    const int64_t o = offsets[i], sz = sizes[i];
+    TORCH_CHECK(o >= 0 && sz >= 1, "layer_tables: variable ", i, " has offset ", o, ", size ", sz);
+    TORCH_CHECK(o % 4 == 0, "layer_tables: variable ", i, " starts at ", o, ", not a multiple of 4 floats");
+    if (i > 0) {
+      TORCH_CHECK(o >= offsets[i - 1], "layer_tables: variables are not sorted by offset (variable ", i, ")");
+      TORCH_CHECK(o >= end, "layer_tables: variable ", i, " at ", o, " overlaps its predecessor, which ends at ", end);
+    }
+    TORCH_CHECK(sz <= n && o <= n - sz, "layer_tables: variable ", i, " [", o, ", ", o + sz, ") ends past the slab's ",
+                n, " elements");
+    end = o + sz;
+    first.push_back((int32_t)(chunks.size() / 4));
+    for (int64_t p = 0; p < sz; p += chunk) {
+      chunks.push_back((int32_t)(o + p));
+      chunks.push_back((int32_t)std::min<int64_t>(chunk, sz - p));
+      chunks.push_back((int32_t)i);
+      chunks.push_back(0);
+    }
+  }
+  first.push_back((int32_t)(chunks.size() / 4));
+  LayerTables t;
+  t.V = (int64_t)V;
+  t.C = (int64_t)chunks.size() / 4;
+  t.n = n;
+  t.chunk = chunk;
+  std::vector<float> wdf(wd.begin(), wd.end());
+  std::vector<int32_t> ad(adapt.begin(), adapt.end());
+  const auto i32 = at::TensorOptions().dtype(at::kInt);
+  const auto dev = at::Device(at::kCUDA, c10::hip::current_device());
+  const auto f32 = at::TensorOptions().dtype(at::kFloat);
+  auto upload = [&](void* p, at::IntArrayRef shape, const at::TensorOptions& o) {
+    return p == nullptr ? at::empty(shape, o.device(dev)) : at::from_blob(p, shape, o).clone().to(dev);
+  };
+  t.chunks = upload(t.C ? chunks.data() : nullptr, {t.C, 4}, i32);
+  t.first_chunk = upload(first.data(), {t.V + 1}, i32);
+  t.wd = upload(t.V ? wdf.data() : nullptr, {t.V}, f32);
+  t.adapt = upload(t.V ? ad.data() : nullptr, {t.V}, i32);
+  return t;
+}
+
+LayerTables layer_tables(std::vector<int64_t> offsets, std::vector<int64_t> sizes, int64_t n, std::vector<double> wd,
+                         std::vector<bool> adapt) {
+  return layer_tables_chunk(std::move(offsets), std::move(sizes), n, std::move(wd), std::move(adapt), tdl::kLayerChunk);
+}
+
+// an n-element slab operand of a layer-wise launch
+float* layer_slab(const at::Tensor& t, const LayerTables& T, const char* name) {
+  check_slab_f32(t, name);
+  TORCH_CHECK(t.get_device() == T.chunks.get_device(), name, " is not on the layer tables' device");
+  TORCH_CHECK(t.numel() >= T.n, name, " is too short: ", t.numel(), " < ", T.n, " elements");
+  TORCH_CHECK(t.numel() == T.n, "the layer tables were built for n = ", T.n, ", ", name, " has ", t.numel());
+  return t.data_ptr<float>();
+}
+
+double* layer_partials(const at::Tensor& p, const LayerTables& T) {
+  TORCH_CHECK(p.is_cuda() && p.is_contiguous() && p.scalar_type() == at::kDouble,
+              "partials must be a contiguous float64 GPU tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p.data_ptr()) % 16 == 0, "partials must be 16-byte aligned");
+  TORCH_CHECK(p.numel() >= 2 * T.C, "partials too small: ", p.numel(), " < ", 2 * T.C);
+  return p.data_ptr<double>();
+}
+
+float* layer_words(const at::Tensor& t, int64_t need, const char* name) {
+  check_slab_f32(t, name);
+  TORCH_CHECK(t.numel() >= need, name, " too small: ", t.numel(), " < ", need);
+  return t.data_ptr<float>();
+}
+
+tdl::LayerArgs layer_args(const LayerTables& T) {
+  tdl::LayerArgs a{};
+  a.chunks = T.chunks.data_ptr<int>();
+  a.first_chunk = T.first_chunk.data_ptr<int>();
+  a.wd = T.wd.data_ptr<float>();
+  a.adapt = T.adapt.data_ptr<int>();
+  a.V = (int)T.V;
+  a.C = (int)T.C;
+  a.chunk = (int)T.chunk;
+  return a;
+}
+
+void set_layer_clip(tdl::LayerArgs& a, const OptTensor& gscale, const OptDouble& clipvalue) {
+  a.gscale = gscale_ptr(gscale);
+  a.clip = clipvalue.has_value() ? 1 : 0;
+  a.clipvalue = clipvalue.has_value() ? (float)*clipvalue : 0.f;
+}
+
+void set_lamb(tdl::LayerArgs& a, const at::Tensor& t0, int64_t t_add, double b1, double b2, double eps) {
+  check_cuda_f32(t0, "t0");
+  TORCH_CHECK(t0.numel() >= 1, "t0 must hold the step count");
+  a.t0 = t0.data_ptr<float>();
+  a.t_add = (int)t_add;
+  a.b1 = (float)b1;
+  a.b2 = (float)b2;
+  a.eps = (float)eps;
+  TORCH_CHECK(a.b1 > 0.f && a.b1 < 1.f && a.b2 > 0.f && a.b2 < 1.f, "LAMB: beta_1 and beta_2 must lie in (0, 1)");
+  a.lb1 = (float)std::log((double)a.b1);
+  a.lb2 = (float)std::log((double)a.b2);
+}
+
+// launch 1: partials[c] = (sum w^2, sum g'^2) of chunk c
+void lars_sums(const LayerTables& T, at::Tensor w, at::Tensor g, at::Tensor partials, OptTensor gscale,
+               OptDouble clipvalue) {
+  tdl::LayerArgs a = layer_args(T);
+  a.w = layer_slab(w, T, "w");
+  a.g = layer_slab(g, T, "g");
+  a.partials = layer_partials(partials, T);
+  set_layer_clip(a, gscale, clipvalue);
+  tdl::layer_sums_apply(a, false, cur_stream());
+}
+
+// launch 1: m, v updated in place; partials[c] = (sum w^2, sum u^2) of chunk c
+void lamb_sums(const LayerTables& T, at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, at::Tensor partials,
+               at::Tensor t0, int64_t t_add, double b1, double b2, double eps, OptTensor gscale,
+               OptDouble clipvalue) {
+  tdl::LayerArgs a = layer_args(T);
+  a.w = layer_slab(w, T, "w");
+  a.g = layer_slab(g, T, "g");
+  a.s0 = layer_slab(m, T, "m");
+  a.s1 = layer_slab(v, T, "v");
+  a.partials = layer_partials(partials, T);
+  set_lamb(a, t0, t_add, b1, b2, eps);
+  set_layer_clip(a, gscale, clipvalue);
+  tdl::layer_sums_apply(a, true, cur_stream());
+}
+
+// launch 2: ratio[v], norms[v] = (|w_v|, |g'_v| or |u_v|) from the chunk sums
+void layer_ratio(const LayerTables& T, at::Tensor partials, at::Tensor ratio, at::Tensor norms, bool lamb,
+                 double eeta, double eps) {
+  tdl::LayerArgs a = layer_args(T);
+  a.partials = layer_partials(partials, T);
+  a.ratio = layer_words(ratio, T.V, "ratio");
+  a.norms = layer_words(norms, 2 * T.V, "norms");
+  TORCH_CHECK(ratio.get_device() == T.chunks.get_device() && norms.get_device() == T.chunks.get_device() &&
+                  partials.get_device() == T.chunks.get_device(), "operands are not on the layer tables' device");
+  a.eeta = (float)eeta;
+  a.eps = (float)eps;
+  tdl::layer_ratio_apply(a, lamb, cur_stream());
+}
+
+void lars_ratio(const LayerTables& T, at::Tensor partials, at::Tensor ratio, at::Tensor norms, double eeta,
+                double eps) {
+  layer_ratio(T, partials, ratio, norms, false, eeta, eps);
+}
+
+void lamb_ratio(const LayerTables& T, at::Tensor partials, at::Tensor ratio, at::Tensor norms) {
+  layer_ratio(T, partials, ratio, norms, true, 0.0, 0.0);
+}
+
+// launch 3
+void lars_update(const LayerTables& T, at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor ratio, at::Tensor lr,
+                 double momentum, bool nesterov, OptTensor gscale, OptDouble clipvalue) {
+  tdl::LayerArgs a = layer_args(T);
+  a.w = layer_slab(w, T, "w");
+  a.g = layer_slab(g, T, "g");
+  a.s0 = layer_slab(v, T, "v");
+  a.ratio = layer_words(ratio, T.V, "ratio");
+  check_cuda_f32(lr, "lr");
+  TORCH_CHECK(lr.numel() >= 1, "lr must hold the learning rate");
+  a.lr = lr.data_ptr<float>();
+  a.b1 = (float)momentum;
+  a.nesterov = nesterov ? 1 : 0;
+  set_layer_clip(a, gscale, clipvalue);
+  tdl::lars_apply(a, cur_stream());
+}
+
+void lamb_update(const LayerTables& T, at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor ratio, at::Tensor lr,
+                 at::Tensor t0, int64_t t_add, double b1, double b2, double eps) {
+  tdl::LayerArgs a = layer_args(T);
+  a.w = layer_slab(w, T, "w");
+  a.s0 = layer_slab(m, T, "m");
+  a.s1 = layer_slab(v, T, "v");
+  a.ratio = layer_words(ratio, T.V, "ratio");
+  check_cuda_f32(lr, "lr");
+  TORCH_CHECK(lr.numel() >= 1, "lr must hold the learning rate");
+  a.lr = lr.data_ptr<float>();
+  set_lamb(a, t0, t_add, b1, b2, eps);
+  tdl::lamb_apply(a, cur_stream());
+}
+
 }  // namespace
 
 void register_ops(pybind11::module& m);
@@ -446,6 +643,41 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
   m.def("adagrad", &adagrad, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("acc"), pybind11::arg("lr"),
         pybind11::arg("eps"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+  // layer-wise optimizers (csrc/kernels/layerwise.hip): host-validated tables, then three launches per step
+  m.attr("LAYER_CHUNK") = (int64_t)tdl::kLayerChunk;  // largest chunk of a variable (one workgroup)
+  pybind11::class_<LayerTables>(m, "LayerTables")
+      .def_readonly("chunks", &LayerTables::chunks)
+      .def_readonly("first_chunk", &LayerTables::first_chunk)
+      .def_readonly("wd", &LayerTables::wd)
+      .def_readonly("adapt", &LayerTables::adapt)
+      .def_readonly("V", &LayerTables::V)
+      .def_readonly("C", &LayerTables::C)
+      .def_readonly("n", &LayerTables::n)
+      .def_readonly("chunk", &LayerTables::chunk);
+  m.def("layer_tables", &layer_tables,
+        "validated chunk tables of the variables [offsets[i], offsets[i] + sizes[i]) of an n-element slab, on the "
+        "current device",
+        pybind11::arg("offsets"), pybind11::arg("sizes"), pybind11::arg("n"), pybind11::arg("wd"),
+        pybind11::arg("adapt"));
+  m.def("layer_tables_chunk", &layer_tables_chunk, "layer_tables at another chunk size (measurement only)",
+        pybind11::arg("offsets"), pybind11::arg("sizes"), pybind11::arg("n"), pybind11::arg("wd"),
+        pybind11::arg("adapt"), pybind11::arg("chunk"));
+  m.def("lars_sums", &lars_sums, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("g"),
+        pybind11::arg("partials"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+  m.def("lamb_sums", &lamb_sums, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("m"),
+        pybind11::arg("v"), pybind11::arg("partials"), pybind11::arg("t0"), pybind11::arg("t_add"),
+        pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("gscale") = none,
+        pybind11::arg("clipvalue") = none);
+  m.def("lars_ratio", &lars_ratio, pybind11::arg("tables"), pybind11::arg("partials"), pybind11::arg("ratio"),
+        pybind11::arg("norms"), pybind11::arg("eeta"), pybind11::arg("eps"));
+  m.def("lamb_ratio", &lamb_ratio, pybind11::arg("tables"), pybind11::arg("partials"), pybind11::arg("ratio"),
+        pybind11::arg("norms"));
+  m.def("lars_update", &lars_update, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("g"),
+        pybind11::arg("v"), pybind11::arg("ratio"), pybind11::arg("lr"), pybind11::arg("momentum"),
+        pybind11::arg("nesterov"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+  m.def("lamb_update", &lamb_update, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("m"),
+        pybind11::arg("v"), pybind11::arg("ratio"), pybind11::arg("lr"), pybind11::arg("t0"), pybind11::arg("t_add"),
+        pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"));
   register_ops(m);
   register_comm(m);
   register_rccl(m);

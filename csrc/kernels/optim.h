@@ -73,4 +73,47 @@ inline int64_t clip_partials_count(int64_t n, int64_t chunk = kClipChunk) { retu
 void clip_norm_apply(const float* g, double* partials, float* out, int64_t n, float clipnorm, bool clamp,
                      float clipvalue, hipStream_t s, int chunk = kClipChunk);
 
+// Layer-wise adaptive updates (layerwise.hip): LARS and LAMB, whose step depends on two norms of each
+// element's own variable, in three launches over the slab -- chunk sums, per-variable trust ratios, update.
+//
+// Layer tables (built and validated on the host, bindings.cpp layer_tables): chunks[C][4] = (start, len,
+// var, 0) with every chunk inside one variable, 1 <= len <= kLayerChunk, start % 4 == 0, a variable's
+// chunks consecutive and ascending; first_chunk[V + 1]; per variable wd[V] (f32) and adapt[V] (int32).
+// kLayerChunk is a compile-time constant, never derived from the device or the grid: the order of the
+// sums hangs on it.  Measured candidates (profiles/layerwise_cost.txt, us for the three launches): at
+// ResNet-50's 25.6 M parameters 2048 / 4096 / 8192 tie (LARS 112 / 111 / 112, LAMB 185 / 190 / 187: the bytes
+// decide); at the reference CNN's 225 k LARS ties at 9.9 (three launch latencies) and LAMB takes 10.2 / 12.0 /
+// 15.7: 8192 leaves 34 workgroups of one wave per SIMD, each with 32 elements of divide / sqrt latency per
+// thread and nothing to hide it behind.  kClipChunk's 8192 suits a kernel that only squares and adds.
+constexpr int kLayerChunk = 2048;
+struct LayerArgs {
+  float* w;
+  const float* g;       // (k_lamb_apply does not read it)
+  float* s0;            // LARS momentum / LAMB m
+  float* s1;            // LAMB v
+  const int* chunks;
+  const int* first_chunk;
+  const float* wd;
+  const int* adapt;
+  double* partials;     // [C][2]: chunk sums of w^2 and of g'^2 (LARS) / u^2 (LAMB)
+  float* ratio;         // [V]
+  float* norms;         // [V][2]: |w_i| and |g'_i| / |u_i|
+  const float* lr;      // device learning rate
+  const float* t0;      // LAMB: device step count of the execution's first step (see OptimArgs)
+  int t_add;
+  int V, C;
+  int chunk;            // the tables' chunk size: kLayerChunk, or a measured candidate (4096 / 8192)
+  float b1, b2, eps;    // LAMB beta_1 / beta_2 / epsilon; LARS momentum / - / epsilon
+  float lb1, lb2;       // LAMB: log beta_1, log beta_2 (taken in f64 on the host)
+  float eeta;           // LARS trust coefficient
+  int nesterov;
+  const float* gscale;  // gradient clipping, as in OptimArgs
+  float clipvalue;
+  int clip;
+};
+void layer_sums_apply(const LayerArgs& a, bool lamb, hipStream_t s);   // launch 1
+void layer_ratio_apply(const LayerArgs& a, bool lamb, hipStream_t s);  // launch 2
+void lars_apply(const LayerArgs& a, hipStream_t s);                    // launch 3
+void lamb_apply(const LayerArgs& a, hipStream_t s);
+
 }  // namespace tdl

@@ -87,13 +87,15 @@ def eligible(model, dataset=None) -> Optional[str]:
             lo.reduction in (losses.Reduction.AUTO, losses.Reduction.SUM_OVER_BATCH_SIZE)):
         return "loss is not SparseCategoricalCrossentropy(from_logits=True)"
     opt = model.optimizer
-    if type(opt) not in (optimizers.SGD, optimizers.Adam, optimizers.AdamW, optimizers.RMSprop, optimizers.Adagrad):
+    if type(opt) not in (optimizers.SGD, optimizers.Adam, optimizers.AdamW, optimizers.RMSprop, optimizers.Adagrad,
+                         optimizers.LARS, optimizers.LAMB):
         return f"optimizer {type(opt).__name__} has no fused update"
     if opt._clipped and not hasattr(ops.hip(), "clip_norm"):
         return "the extension has no clip_norm kernel (rebuild: python build_native.py)"
     if opt.weight_decay and not isinstance(opt, optimizers.Adam):
         return "decoupled weight decay is fused for Adam/AdamW only"
-    kern = {"Adam": "adam", "AdamW": "adam", "RMSprop": "rmsprop", "Adagrad": "adagrad"}.get(type(opt).__name__)
+    kern = {"Adam": "adam", "AdamW": "adam", "RMSprop": "rmsprop", "Adagrad": "adagrad", "LARS": "layer_tables",
+            "LAMB": "layer_tables"}.get(type(opt).__name__)
     if kern is not None and not hasattr(ops.hip(), kern):
         return f"the extension has no {kern} kernel (rebuild: python build_native.py)"
     for m in model.compiled_metrics:
@@ -135,6 +137,7 @@ class FusedMnistTrainer:
         for v in model._trainable_vars:
             v._leaf = None
         self.optimizer = model.optimizer
+        self.optimizer.set_layout(model._layout)
         self.optimizer.build(self.W.numel(), self.device)
         self.K = max(1, int(model._steps_per_execution))
         self.metrics_dev = torch.zeros(4, dtype=torch.float32, device=self.device)

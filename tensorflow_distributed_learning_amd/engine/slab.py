@@ -65,6 +65,11 @@ class SlabLayout:
     def named_views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
         return {s.name: self.view(flat, i) for i, s in enumerate(self.specs)}
 
+    def layer_spans(self) -> Tuple[List[int], List[int], List[str]]:
+        """(offsets, sizes, names) of the variables, in slab order: what a per-variable (layer-wise)
+        optimizer needs of the layout."""
+        return list(self.offsets), [s.size for s in self.specs], [s.name for s in self.specs]
+
     @property
     def num_params(self) -> int:
         return sum(s.size for s in self.specs)

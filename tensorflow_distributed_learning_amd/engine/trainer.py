@@ -144,6 +144,7 @@ class GenericTrainer:
         self.W, self.G = model._W, model._G
         self._make_leaves()
         self.optimizer = model.optimizer
+        self.optimizer.set_layout(model._layout)
         self.optimizer.build(self.W.numel(), self.device)
         self.loss = model.loss
         self.loss_tracker = model._loss_tracker

@@ -14,6 +14,16 @@ and the update kernel applies ``clamp(g, +-clipvalue) * scale`` where it loads `
 over the gradient, no torch reduction, capturable.  The torch formulas (``_clip`` + ``_update``)
 remain the CPU implementation.  Their f32 sum of squares overflows to inf for a gradient norm above
 ~1.8e19, where the device path's f64 sum still returns the finite norm.
+
+LARS and LAMB, the optimizers of large-batch data-parallel training, scale every element's step by a
+trust ratio of two norms of its own variable, so they read the slab's layout (``set_layout``, which
+the engines call before ``build``).  On the GPU a step is three launches whatever the number of
+variables (``_C.lars_sums`` / ``lars_ratio`` / ``lars_update`` and the ``lamb_`` three;
+csrc/kernels/layerwise.hip): f64 sums of squares per chunk of a variable, the per-variable norms
+and ratios from them in a fixed order (bit-identical on every run and replica), the update.  The
+chunk tables are built and validated once on the host (``_C.layer_tables``).  ``last_layer_ratios``
+/ ``last_layer_norms`` expose the last step's words.  The per-variable torch formulas are the CPU
+implementation.  ``clipnorm`` stays one norm over the whole slab for every optimizer.
 """
 from __future__ import annotations
 
@@ -92,6 +102,13 @@ class Optimizer:
         otherwise (the caller then uses apply_flat).  ``t_add``: the step's offset inside an
         execution whose first step is t_dev (Adam)."""
         return False
+
+    def set_layout(self, layout):
+        """The slab's ``SlabLayout`` (the engines pass it just before ``build``).  Only the layer-wise
+        optimizers (LARS, LAMB) read it: their step depends on per-variable norms."""
+        self._layout = layout
+
+    _layout = None
 
     # ------------------------------------------------------------------ slots
     def build(self, n: int, device: torch.device):
@@ -452,7 +469,257 @@ class Adagrad(Optimizer):
         W.addcdiv_(G, acc.sqrt().add_(self.epsilon), value=-self.current_lr())
 
 
-_ALIASES = {"sgd": SGD, "adam": Adam, "adamw": AdamW, "rmsprop": RMSprop, "adagrad": Adagrad}
+def _f32(x) -> float:
+    """``x`` rounded to f32 (the value a kernel receives), as a Python float."""
+    return torch.tensor(float(x), dtype=torch.float32).item()
+
+
+class _Layerwise(Optimizer):
+    """Shared base of LARS and LAMB: the step of every element is scaled by a trust ratio of two norms of
+    its own variable, so the optimizer needs the slab's layout (``set_layout``).
+
+    Variable i has a decay ``weight_decay_rate`` (0 if its name matches a pattern of
+    ``exclude_from_weight_decay``) and takes part in the layer adaptation unless its name matches a pattern
+    of ``exclude_from_layer_adaptation`` (default: the decay list); patterns are ``re.search`` on the
+    variable's name.  The decay is part of the update direction, not the base class's decoupled
+    ``weight_decay`` (which stays None).
+
+    On a GPU slab the step is ``clip_norm`` (if clipped) + three launches of csrc/kernels/layerwise.hip over
+    host-validated layer tables; every buffer is allocated in ``build()``, before any capture.  On the CPU
+    ``_update`` applies the torch formulas over per-variable views, with f32 torch norms as in ``_clip``.
+    """
+
+    def __init__(self, learning_rate, name, weight_decay_rate=0.0, exclude_from_weight_decay=None,
+                 exclude_from_layer_adaptation=None, **kw):
+        super().__init__(learning_rate, name, **kw)
+        self.weight_decay_rate = float(weight_decay_rate)
+        self.exclude_from_weight_decay = None if exclude_from_weight_decay is None else list(exclude_from_weight_decay)
+        self.exclude_from_layer_adaptation = None if exclude_from_layer_adaptation is None else list(
+            exclude_from_layer_adaptation)
+        self._built_layout = None
+        self._spans = self._wd = self._adapt = None
+        self._tables = self._layer_partials = self._layer_ratio = self._layer_norms = None
+        self._cpu_ratios: Optional[List[float]] = None  # the last CPU step's ratios (host floats)
+
+    def layer_operands(self, layout):
+        """(decay per variable, adapt flag per variable) of ``layout`` under the exclusion patterns."""
+        import re
+
+        names = layout.layer_spans()[2]
+        dec = self.exclude_from_weight_decay or []
+        ada = dec if self.exclude_from_layer_adaptation is None else self.exclude_from_layer_adaptation
+        wd = [0.0 if any(re.search(p, n) for p in dec) else self.weight_decay_rate for n in names]
+        adapt = [not any(re.search(p, n) for p in ada) for n in names]
+        return wd, adapt
+
+    def build(self, n: int, device: torch.device):
+        lay = self._layout
+        if lay is None:
+            raise ValueError(f"{type(self).__name__} is a layer-wise optimizer and needs the slab layout: call "
+                             "set_layout(layout) before build() / apply_flat() (model.fit and apply_gradients do)")
+        if lay.total != n:
+            raise ValueError(f"{type(self).__name__}: the layout covers {lay.total} elements, the slab has {n}")
+        if self._n == n and self._device == device and self._built_layout is lay:
+            return
+        self._n = None
+        super().build(n, device)
+        self._built_layout = lay
+        self._spans = lay.layer_spans()
+        self._wd, self._adapt = self.layer_operands(lay)
+        self._tables = self._layer_partials = self._layer_ratio = self._layer_norms = None
+        if device.type == "cuda" and _kernel_present("layer_tables"):
+            from .. import ops
+
+            V = len(self._wd)
+            with torch.cuda.device(device):
+                self._tables = ops.hip().layer_tables(self._spans[0], self._spans[1], n, self._wd, self._adapt)
+            self._layer_partials = torch.zeros(max(2, 2 * self._tables.C), dtype=torch.float64, device=device)
+            self._layer_ratio = torch.ones(max(1, V), dtype=torch.float32, device=device)
+            self._layer_norms = torch.zeros(max(1, V), 2, dtype=torch.float32, device=device)
+
+    @property
+    def last_layer_ratios(self) -> Optional[torch.Tensor]:
+        """The trust ratios of the last device step, one per variable (a device view; None on the CPU)."""
+        return None if self._tables is None else self._layer_ratio[:self._tables.V]
+
+    @property
+    def last_layer_norms(self) -> Optional[torch.Tensor]:
+        """[V, 2] of the last device step: |w_i| and |g'_i| (LARS) or |u_i| (LAMB); None on the CPU."""
+        return None if self._tables is None else self._layer_norms[:self._tables.V]
+
+    @property
+    def graph_safe(self) -> bool:
+        """The kernels are present, the optimizer is built on a GPU slab and any clipping runs on the device
+        (see Adam.graph_safe)."""
+        return self._tables is not None and self._clip_on_device
+
+    def device_update(self, W, G, t_add=0):
+        """csrc/kernels/layerwise.hip: chunk sums, per-variable ratios, update."""
+        if W.device.type != "cuda" or W.dtype != torch.float32:
+            return False
+        if self._tables is None or not self._clip_on_device:
+            raise RuntimeError(f"{type(self).__name__}: the extension has no layer_tables / clip_norm kernel for "
+                               "the GPU slab (rebuild: python build_native.py)")
+        if W.numel() != self._n:
+            raise RuntimeError(f"{type(self).__name__} updates the whole slab ({self._n} elements), got {W.numel()}")
+        from .. import ops
+
+        self._launch(ops.hip(), W, G, int(t_add), self.device_clip(G))
+        return True
+
+    def _launch(self, C, W, G, t_add, clip):
+        raise NotImplementedError
+
+    def _views(self, *flats):
+        offs, sizes, _ = self._spans
+        for i, (o, s) in enumerate(zip(offs, sizes)):
+            yield (i,) + tuple(f[o:o + s] for f in flats)
+
+    def _apply_gradients_now(self, gv):
+        """Custom loops: the variables passed are packed into an aligned slab of their own layout, so the
+        same kernels (and the same formulas on the CPU) serve them."""
+        if not gv:
+            return
+        from ..engine.slab import SlabLayout
+
+        items = tuple((str(getattr(v, "name", f"variable_{i}")), tuple(int(d) for d in v.shape))
+                      for i, (_, v) in enumerate(gv))
+        if getattr(self, "_eager_items", None) != items:
+            self.set_layout(SlabLayout.from_shapes(items))
+            self._eager_items = items
+        lay = self._layout
+        dev = gv[0][1].read_value().device
+        W = lay.pack([v.read_value().float() for _, v in gv], device=dev)
+        G = lay.pack([torch.as_tensor(g).float() for g, _ in gv], device=dev)
+        self.build(W.numel(), W.device)
+        self.apply_flat(W, G)
+        for (_, v), view in zip(gv, lay.views(W)):
+            v.assign(view)
+
+    def get_config(self):
+        return dict(super().get_config(), weight_decay_rate=self.weight_decay_rate,
+                    exclude_from_weight_decay=self.exclude_from_weight_decay,
+                    exclude_from_layer_adaptation=self.exclude_from_layer_adaptation)
+
+
+class LARS(_Layerwise):
+    """Layer-wise Adaptive Rate Scaling (You, Gitman, Ginsburg 2017), with the arguments of
+    ``tf.contrib.opt.LARSOptimizer`` / tf-models ``LARS``:
+
+        r_i = eeta |w_i| / (|g_i| + wd_i |w_i| + epsilon)  if variable i adapts and |w_i| > 0 and |g_i| > 0, else 1
+        d = g + wd_i w,  s = lr r_i,  v <- momentum v - s d,  w <- w + v   (nesterov: w <- w + momentum v - s d)
+
+    i.e. this package's momentum SGD with ``lr`` replaced by ``s`` and ``g`` by ``d``; ``g`` is the gradient
+    after clipping.  Norms in f64 on the device, in f32 on the CPU.  TF-addons and tf-models are not installed
+    where this was written: parity with their implementations is unpinned.
+    """
+
+    def __init__(self, learning_rate=0.01, momentum=0.9, weight_decay_rate=0.0, eeta=0.001, epsilon=0.0,
+                 nesterov=False, exclude_from_weight_decay=None, exclude_from_layer_adaptation=None, name="LARS",
+                 **kw):
+        super().__init__(learning_rate, name, weight_decay_rate, exclude_from_weight_decay,
+                         exclude_from_layer_adaptation, **kw)
+        if not 0.0 <= momentum <= 1.0:
+            raise ValueError("momentum must be in [0, 1]")
+        self.momentum, self.eeta, self.epsilon, self.nesterov = float(momentum), float(eeta), float(epsilon), bool(
+            nesterov)
+
+    def _slot_names(self):
+        return ["momentum"]
+
+    def _launch(self, C, W, G, t_add, clip):
+        T = self._tables
+        C.lars_sums(T, W, G, self._layer_partials, **clip)
+        C.lars_ratio(T, self._layer_partials, self._layer_ratio, self._layer_norms, self.eeta, self.epsilon)
+        C.lars_update(T, W, G, self._slots["momentum"], self._layer_ratio, self.lr_dev, self.momentum, self.nesterov,
+                      **clip)
+
+    def _update(self, W, G):
+        lr, mu = _f32(self.current_lr()), self.momentum
+        eeta, eps = _f32(self.eeta), _f32(self.epsilon)
+        self._cpu_ratios = []
+        for i, w, g, v in self._views(W, G, self._slots["momentum"]):
+            wd, r = self._wd[i], 1.0
+            if self._adapt[i]:
+                nw, ng = float(torch.linalg.vector_norm(w)), float(torch.linalg.vector_norm(g))
+                if nw > 0 and ng > 0:
+                    r = _f32(eeta * nw / (ng + _f32(wd) * nw + eps))
+            self._cpu_ratios.append(r)
+            s = _f32(lr * r)
+            d = g.add(w, alpha=wd) if wd else g
+            v.mul_(mu).add_(d, alpha=-s)
+            if self.nesterov:
+                w.add_(v, alpha=mu).add_(d, alpha=-s)
+            else:
+                w.add_(v)
+
+    def get_config(self):
+        return dict(super().get_config(), momentum=self.momentum, eeta=self.eeta, epsilon=self.epsilon,
+                    nesterov=self.nesterov)
+
+
+class LAMB(_Layerwise):
+    """Layer-wise Adaptive Moments for Batch training (You et al. 2019), with the arguments of
+    ``tfa.optimizers.LAMB``; t = iterations + 1:
+
+        m <- beta_1 m + (1 - beta_1) g,   v <- beta_2 v + (1 - beta_2) g^2
+        u = (m / (1 - beta_1^t)) / (sqrt(v / (1 - beta_2^t)) + epsilon) + wd_i w
+        r_i = |w_i| / |u_i|  if variable i adapts and |w_i| > 0 and |u_i| > 0, else 1
+        w <- w - lr r_i u
+
+    ``g`` is the gradient after clipping.  Norms in f64 on the device, in f32 on the CPU.  TF-addons is not
+    installed where this was written: parity with its implementation is unpinned.
+    """
+
+    _needs_step = True
+
+    def __init__(self, learning_rate=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-6, weight_decay_rate=0.0,
+                 exclude_from_weight_decay=None, exclude_from_layer_adaptation=None, name="LAMB", **kw):
+        super().__init__(learning_rate, name, weight_decay_rate, exclude_from_weight_decay,
+                         exclude_from_layer_adaptation, **kw)
+        if not (0.0 < beta_1 < 1.0 and 0.0 < beta_2 < 1.0):
+            raise ValueError("beta_1 and beta_2 must lie in (0, 1)")
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+
+    def _slot_names(self):
+        return ["m", "v"]
+
+    def _launch(self, C, W, G, t_add, clip):
+        T, m, v = self._tables, self._slots["m"], self._slots["v"]
+        hp = (self.t_dev, t_add, self.beta_1, self.beta_2, self.epsilon)
+        C.lamb_sums(T, W, G, m, v, self._layer_partials, *hp, **clip)
+        C.lamb_ratio(T, self._layer_partials, self._layer_ratio, self._layer_norms)
+        C.lamb_update(T, W, m, v, self._layer_ratio, self.lr_dev, *hp)
+
+    def _update(self, W, G):
+        lr = _f32(self.current_lr())
+        # the bias corrections 1 - beta^t in f64 from the f32 betas, rounded once (the kernels reach the same
+        # f32 values to a few ulp as -expm1f(t log beta); the plain f32 difference cancels)
+        t = self.iterations + 1
+        c1, c2 = _f32(1.0 - _f32(self.beta_1) ** t), _f32(1.0 - _f32(self.beta_2) ** t)
+        self._cpu_ratios = []
+        for i, w, g, m, v in self._views(W, G, self._slots["m"], self._slots["v"]):
+            m.mul_(self.beta_1).add_(g, alpha=1 - self.beta_1)
+            v.mul_(self.beta_2).addcmul_(g, g, value=1 - self.beta_2)
+            u = m.div(c1).div_(v.div(c2).sqrt_().add_(self.epsilon))
+            if self._wd[i]:
+                u.add_(w, alpha=self._wd[i])
+            r = 1.0
+            if self._adapt[i]:
+                nw, nu = float(torch.linalg.vector_norm(w)), float(torch.linalg.vector_norm(u))
+                if nw > 0 and nu > 0:
+                    r = _f32(nw / nu)
+            self._cpu_ratios.append(r)
+            w.add_(u, alpha=-_f32(lr * r))
+
+    def get_config(self):
+        return dict(super().get_config(), beta_1=self.beta_1, beta_2=self.beta_2, epsilon=self.epsilon)
+
+
+Lamb = LAMB
+
+_ALIASES = {"sgd": SGD, "adam": Adam, "adamw": AdamW, "rmsprop": RMSprop, "adagrad": Adagrad, "lars": LARS,
+            "lamb": LAMB}
 
 
 def get(identifier) -> Optimizer:
