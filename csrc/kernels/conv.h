@@ -2,12 +2,17 @@
 // GEMMs: no im2col buffer, the operand loaders gather the receptive fields straight from the NHWC
 // activations.  Used by keras.layers.Conv2D for bf16 activations on the GPU (ResNet-50, BASELINE
 // configs 4/5) when the per-shape autotuner (keras/conv_select.py) measures it faster than MIOpen.
-// f32 accumulation; outputs are rounded to bf16 once, in the epilogue.
+// f32 accumulation; outputs are rounded to bf16 once, in the epilogue (to nearest even; a finite f32 sum
+// halfway to the bf16 infinity rounds to Inf).  Subnormals are IEEE throughout: bf16 subnormal operands
+// take part in the MFMAs, f32 subnormal sums are kept and stored as bf16 subnormals -- nothing flushes
+// (tests/test_conv_edges_gpu.py, test_conv_wgrad_edges_gpu.py).  A NaN or Inf operand reaches exactly the
+// outputs whose receptive field holds it; the one exception is documented at conv_wgrad3x3_c64.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
 #include <vector>
 
 namespace tdl {
@@ -63,6 +68,21 @@ void conv_dgrad_s2_1x1_bf16(const void* dy, const void* w_hwio, void* dx, const 
                             const float* bn_ss = nullptr);
 int conv_dgrad_s2_row_tile(const ConvGeom& g);
 
+// The kernel the launch of a geometry takes under the current A/B hooks, by name, and its row tile (the
+// rows per partial-sum row of its epilogue).  The launch itself dispatches on the same selection, so the
+// answer cannot drift from what runs; no device is touched.  direction 0: conv_fwd_bf16 (in_bn: with
+// in_ss), 1: conv_dgrad_bf16, 2: conv_dgrad_s2_1x1_bf16 (bn: with bn_part; bn_ss: with bn_part and bn_ss).
+// Names: igemm[_inbn]_<BM>x<BN>_d<DEPTH>_ek<EK> (k_conv_igemm), glds_ring_<BM>x<BN>_ek<EK> and
+// glds_dma1_<BM>x<BN>_w<waves per SIMD>_mf<MFMA form>_ek<EK> (k_conv_glds), halo_<BM>x<BN>_ek<EK>
+// (k_conv_halo); EK 0 plain (+ residual, + statistics), 1 BN-group backward with the mask from bn_y,
+// 2 stride-2 scatter (+ BN group), 3 BN-group backward with the mask from bn_ss.
+struct ConvSelected {
+  std::string name;
+  int row_tile;
+};
+ConvSelected conv_selected(int direction, const ConvGeom& g, bool bn, bool bn_ss, bool in_bn);
+std::vector<std::string> conv_kernel_names();  // every name conv_selected can return
+
 // Weight gradient, split-K over output pixels with a deterministic partial-slab reduction.
 struct WgradPlan {
   int wmw, wnw;        // workgroup tile: (64 wmw) output channels x (64 wnw) (kh, kw, c) columns
@@ -86,6 +106,9 @@ void conv_wgrad_bf16(const void* x, const void* dy, float* ws, const WgradPlan& 
 
 // Weight gradient of a 3x3 / stride 1 / pad 1 conv with C == 64 (wgrad3x3.hip): whole output rows per
 // workgroup, the 9 x 64 x 64 tile in registers, deterministic slice reduction.  ws: ..._ws_elems f32.
+// Non-finite x: with W % 32 != 0, a NaN / Inf in x's last column also makes the kw = 0 entries (kh, 0, c, :)
+// of the taps that read its row NaN (0 * x in the padded pixel of the 32-pixel step), besides the kw = 1, 2
+// entries that read it; finite inputs are unaffected.
 bool conv_wgrad3x3_c64_supported(const ConvGeom& g);
 long long conv_wgrad3x3_c64_ws_elems(const ConvGeom& g);
 void conv_wgrad3x3_c64(const void* x, const void* dy, float* ws, void* dw_bf16, float* dw_f32, bool accumulate,

@@ -20,9 +20,12 @@
 // are adjacent), and the row block's activations are read into one L2 instead of eight.
 #include <algorithm>
 #include <array>
+#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <mutex>
+#include <string>
+#include <vector>
 
 #include "kernels/conv.h"
 #include "kernels/common.h"
@@ -999,18 +1002,67 @@ int halo_window(const Igemm& a, int& Hp, int& Wp) {
 int g_depth = 2;  // main-loop variant; conv_force_depth for A/B sweeps
 bool g_single = true;  // default: the single-stage, 4-waves-per-SIMD variant for every reduction length
 
-template <int BM, int BN, int DEPTH>
-void launch_epi(const Igemm& a, hipStream_t s) {
-  const dim3 grid((a.M + BM - 1) / BM * (a.K / BN)), block(BM * 2);
-  {
-    if (a.scatter)  // (the scatter epilogue spills at 128 VGPRs: depth 0 takes the 3-waves-per-SIMD variant)
-      hipLaunchKernelGGL((k_conv_igemm<BM, BN, DEPTH == 0 ? 3 : DEPTH, 2>), grid, block, 0, s, a);
-    else if (a.bn_part && a.bn_ss)  // (DEPTH 3's fused BN-group backward epilogue spills at 168 VGPRs: depth 2)
-      hipLaunchKernelGGL((k_conv_igemm<BM, BN, DEPTH == 3 ? 2 : DEPTH, 3>), grid, block, 0, s, a);
-    else if (a.bn_part)
-      hipLaunchKernelGGL((k_conv_igemm<BM, BN, DEPTH == 3 ? 2 : DEPTH, 1>), grid, block, 0, s, a);
-    else
-      hipLaunchKernelGGL((k_conv_igemm<BM, BN, DEPTH, 0>), grid, block, 0, s, a);
+// What select() decides for one launch: the main loop, the workgroup tile, the epilogue and, where the
+// main loop has more than one, the pipeline depth / MFMA form / occupancy target.  launch() dispatches on
+// exactly these fields (nothing else picks a kernel), and conv_selected() reports them by name.
+enum ConvLoop { kLoopIgemm = 0, kLoopIgemmInBn, kLoopRing, kLoopDma1, kLoopHalo };
+struct Sel {
+  int loop;    // ConvLoop
+  int bm, bn;  // workgroup tile: bm is the row tile of the epilogue's partial sums
+  int depth;   // k_conv_igemm's DEPTH template argument (0, 1, 2, 3); 0 for the other loops
+  int ek;      // epilogue: 0 plain, 1 BN-group backward (mask from bn_y), 2 stride-2 scatter, 3 EK 1 with the mask from bn_ss
+  int mf;      // MFMA form: 16 (16x16x32) or 32 (32x32x16)
+  int minw;    // dma1: waves per SIMD the kernel is bounded for (4 or 3); 0 for the other loops
+  int Hp, Wp;  // halo: padded geometry
+};
+
+std::string sel_name(const Sel& k) {
+  char b[64];
+  switch (k.loop) {
+    case kLoopIgemm: std::snprintf(b, sizeof b, "igemm_%dx%d_d%d_ek%d", k.bm, k.bn, k.depth, k.ek); break;
+    case kLoopIgemmInBn: std::snprintf(b, sizeof b, "igemm_inbn_%dx%d_d0_ek0", k.bm, k.bn); break;
+    case kLoopRing: std::snprintf(b, sizeof b, "glds_ring_%dx%d_ek%d", k.bm, k.bn, k.ek); break;
+    case kLoopDma1: std::snprintf(b, sizeof b, "glds_dma1_%dx%d_w%d_mf%d_ek%d", k.bm, k.bn, k.minw, k.mf, k.ek); break;
+    default: std::snprintf(b, sizeof b, "halo_%dx%d_ek%d", k.bm, k.bn, k.ek); break;
+  }
+  return b;
+}
+
+// the epilogue a launch carries
+int sel_ek(const Igemm& a) { return a.scatter ? 2 : (a.bn_part && a.bn_ss) ? 3 : a.bn_part ? 1 : 0; }
+
+// k_conv_igemm's DEPTH for a requested main-loop depth and epilogue: the scatter epilogue spills at 128
+// VGPRs (depth 0 takes the 3-waves-per-SIMD variant), DEPTH 3's fused BN-group backward epilogues spill at
+// 168 VGPRs (depth 2)
+int igemm_depth(int depth, int ek) {
+  if (ek == 2) return depth == 0 ? 3 : depth;
+  if (ek == 1 || ek == 3) return depth == 3 ? 2 : depth;
+  return depth;
+}
+
+template <int BM, int BN, int DEPTH, int EK>
+void launch_igemm(const Igemm& a, hipStream_t s) {
+  hipLaunchKernelGGL((k_conv_igemm<BM, BN, DEPTH, EK>), dim3((a.M + BM - 1) / BM * (a.K / BN)), dim3(BM * 2), 0, s, a);
+}
+
+// (depth, ek) as igemm_depth() leaves them: 13 variants per tile
+template <int BM, int BN>
+void launch_tile(const Igemm& a, const Sel& k, hipStream_t s) {
+  switch (k.depth * 4 + k.ek) {
+    case 0 * 4 + 0: return launch_igemm<BM, BN, 0, 0>(a, s);
+    case 0 * 4 + 1: return launch_igemm<BM, BN, 0, 1>(a, s);
+    case 0 * 4 + 3: return launch_igemm<BM, BN, 0, 3>(a, s);
+    case 1 * 4 + 0: return launch_igemm<BM, BN, 1, 0>(a, s);
+    case 1 * 4 + 1: return launch_igemm<BM, BN, 1, 1>(a, s);
+    case 1 * 4 + 2: return launch_igemm<BM, BN, 1, 2>(a, s);
+    case 1 * 4 + 3: return launch_igemm<BM, BN, 1, 3>(a, s);
+    case 2 * 4 + 0: return launch_igemm<BM, BN, 2, 0>(a, s);
+    case 2 * 4 + 1: return launch_igemm<BM, BN, 2, 1>(a, s);
+    case 2 * 4 + 2: return launch_igemm<BM, BN, 2, 2>(a, s);
+    case 2 * 4 + 3: return launch_igemm<BM, BN, 2, 3>(a, s);
+    case 3 * 4 + 0: return launch_igemm<BM, BN, 3, 0>(a, s);
+    case 3 * 4 + 2: return launch_igemm<BM, BN, 3, 2>(a, s);
+    default: std::abort();  // select() never returns another pair
   }
 }
 
@@ -1021,16 +1073,9 @@ void launch_epi(const Igemm& a, hipStream_t s) {
 // us, 14x14 1024->256 1x1 fwd 46.2 -> 40.3): the other workgroups' MFMAs hide a workgroup's load
 // latency and its epilogue better than its own prefetch does.  The single LDS stage with register
 // prefetch at three per CU (DEPTH 3) lands in between.
-template <int BM, int BN>
-void launch_tile(const Igemm& a, hipStream_t s) {
-  if (g_depth == 0 || (g_depth == 2 && g_single))
-    launch_epi<BM, BN, 0>(a, s);
-  else if (g_depth == 3)
-    launch_epi<BM, BN, 3>(a, s);
-  else if (g_depth == 1)
-    launch_epi<BM, BN, 1>(a, s);
-  else
-    launch_epi<BM, BN, 2>(a, s);
+int requested_depth() {
+  if (g_depth == 0 || (g_depth == 2 && g_single)) return 0;
+  return g_depth == 3 ? 3 : (g_depth == 1 ? 1 : 2);
 }
 
 int g_forced_tile = 0;  // 0: heuristic below; 1: 128 x 64, 2: 128 x 128, 3: 256 x 128 (tile sweeps)
@@ -1049,13 +1094,13 @@ int g_impl = [] {  // (TDL_CONV_IMPL: the conv_force_impl A/B hook from the envi
                  // 7: the halo kernel wherever it fits, else the default selection
 
 template <int BM, int BN, int WGM, int WGN, int STAGES = 3, int MINW = 1, int MF = 16>
-void launch_v2(const Igemm& a, hipStream_t s) {
+void launch_v2(const Igemm& a, int ek, hipStream_t s) {
   const dim3 grid((a.M + BM - 1) / BM * (a.K / BN)), block(64 * WGM * WGN);
-  if (a.scatter)
+  if (ek == 2)
     hipLaunchKernelGGL((k_conv_glds<BM, BN, WGM, WGN, 2, STAGES, MINW, MF>), grid, block, 0, s, a);
-  else if (a.bn_part && a.bn_ss)
+  else if (ek == 3)
     hipLaunchKernelGGL((k_conv_glds<BM, BN, WGM, WGN, 3, STAGES, MINW, MF>), grid, block, 0, s, a);
-  else if (a.bn_part)
+  else if (ek == 1)
     hipLaunchKernelGGL((k_conv_glds<BM, BN, WGM, WGN, 1, STAGES, MINW, MF>), grid, block, 0, s, a);
   else
     hipLaunchKernelGGL((k_conv_glds<BM, BN, WGM, WGN, 0, STAGES, MINW, MF>), grid, block, 0, s, a);
@@ -1118,11 +1163,11 @@ bool use_halo(const Igemm& a, int& Hp, int& Wp) {
 }
 
 template <int BN>
-void launch_halo(const Igemm& a, int Hp, int Wp, hipStream_t s) {
+void launch_halo(const Igemm& a, int ek, int Hp, int Wp, hipStream_t s) {
   const dim3 grid((a.M + kHaloBM - 1) / kHaloBM * (a.K / BN)), block(512);
-  if (a.bn_part && a.bn_ss)
+  if (ek == 3)
     hipLaunchKernelGGL((k_conv_halo<kHaloBM, BN, 4, 2, kHaloSlots, 3>), grid, block, 0, s, a, Hp, Wp, g_halo_diag);
-  else if (a.bn_part)
+  else if (ek == 1)
     hipLaunchKernelGGL((k_conv_halo<kHaloBM, BN, 4, 2, kHaloSlots, 1>), grid, block, 0, s, a, Hp, Wp, g_halo_diag);
   else
     hipLaunchKernelGGL((k_conv_halo<kHaloBM, BN, 4, 2, kHaloSlots, 0>), grid, block, 0, s, a, Hp, Wp, g_halo_diag);
@@ -1132,41 +1177,91 @@ void launch_halo(const Igemm& a, int Hp, int Wp, hipStream_t s) {
 // 128 x 128 wins every shape with K % 128 == 0, including the 7x7 ones whose grid is under two
 // workgroups per CU (the 64-column tile's extra LDS traffic per MFMA costs more than the idle CUs);
 // 256 x 128 loses 5-20 % everywhere.  The 64-column tile only serves K == 64 * odd.
-void launch(const Igemm& a, hipStream_t s) {
+// Pure: reads the geometry, which optional operands are present and the A/B hooks; touches no device.
+Sel select(const Igemm& a) {
+  Sel k{kLoopIgemm, 128, a.K % 128 == 0 ? 128 : 64, 0, sel_ek(a), 16, 0, 0, 0};
   if (a.in_ss) {  // input-side BN -> ReLU: the register-staged loader, single stage, plain epilogue
-    if (a.C > kProMaxC) return;  // (conv_fwd_bf16's callers check conv_in_bn_supported)
-    if (a.K % 128 == 0) {
-      hipLaunchKernelGGL((k_conv_igemm<128, 128, 0, 0, true>), dim3((a.M + 127) / 128 * (a.K / 128)), dim3(256), 0, s, a);
-    } else {
-      hipLaunchKernelGGL((k_conv_igemm<128, 64, 0, 0, true>), dim3((a.M + 127) / 128 * (a.K / 64)), dim3(256), 0, s, a);
-    }
-    return;
+    k.loop = kLoopIgemmInBn;
+    k.ek = 0;
+    return k;
   }
-  {
-    int Hp, Wp;
-    if (use_halo(a, Hp, Wp)) {
-      if (a.K % 128 == 0 && g_halo != 3) return launch_halo<128>(a, Hp, Wp, s);
-      return launch_halo<64>(a, Hp, Wp, s);  // (g_halo 3: 64-column tiles everywhere, an A/B arm)
-    }
+  if (use_halo(a, k.Hp, k.Wp)) {
+    k.loop = kLoopHalo;
+    k.bm = kHaloBM;
+    k.mf = 32;
+    if (g_halo == 3) k.bn = 64;  // (g_halo 3: 64-column tiles everywhere, an A/B arm)
+    return k;
   }
   if (use_v2(a.M, a.K, a.KH * a.KW * (a.C / BK), a.KH * a.KW)) {
-    if (a.K % 128 == 0) return launch_v2<256, 128, 4, 2>(a, s);
-    return launch_v2<256, 64, 4, 2>(a, s);
+    k.loop = kLoopRing;
+    k.bm = 256;
+    return k;
   }
   if (use_dma1(a)) {
     // dma1 at 4 waves per SIMD on 32x32x16 (default; impl 6 forces it everywhere) or 16x16x32 MFMAs
     // (impl 4 / TDL_CONV_MFMA=16), or at 3 waves per SIMD (impl 5)
-    const bool mf32 = g_impl == 6 || (g_mf == 32 && g_impl != 4 && g_impl != 5);
-    if (a.K % 128 == 0) {
-      if (mf32) return launch_v2<128, 128, 2, 2, 1, 4, 32>(a, s);
-      return g_impl != 5 ? launch_v2<128, 128, 2, 2, 1, 4>(a, s) : launch_v2<128, 128, 2, 2, 1, 3>(a, s);
-    }
-    if (mf32) return launch_v2<128, 64, 2, 2, 1, 4, 32>(a, s);
-    return g_impl != 5 ? launch_v2<128, 64, 2, 2, 1, 4>(a, s) : launch_v2<128, 64, 2, 2, 1, 3>(a, s);
+    k.loop = kLoopDma1;
+    k.mf = (g_impl == 6 || (g_mf == 32 && g_impl != 4 && g_impl != 5)) ? 32 : 16;
+    k.minw = (k.mf == 16 && g_impl == 5) ? 3 : 4;
+    return k;
   }
-  if (g_forced_tile == 3 && a.K % 128 == 0) return launch_tile<256, 128>(a, s);
-  if (g_forced_tile == 1 || a.K % 128 != 0) return launch_tile<128, 64>(a, s);
-  launch_tile<128, 128>(a, s);
+  if (g_forced_tile == 3 && a.K % 128 == 0) k.bm = 256;
+  if (g_forced_tile == 1) k.bn = 64;
+  k.depth = igemm_depth(requested_depth(), k.ek);
+  return k;
+}
+
+void launch(const Igemm& a, hipStream_t s) {
+  const Sel k = select(a);
+  switch (k.loop) {
+    case kLoopIgemmInBn:
+      if (a.C > kProMaxC) return;  // (conv_fwd_bf16's callers check conv_in_bn_supported)
+      if (k.bn == 128) {
+        hipLaunchKernelGGL((k_conv_igemm<128, 128, 0, 0, true>), dim3((a.M + 127) / 128 * (a.K / 128)), dim3(256), 0, s, a);
+      } else {
+        hipLaunchKernelGGL((k_conv_igemm<128, 64, 0, 0, true>), dim3((a.M + 127) / 128 * (a.K / 64)), dim3(256), 0, s, a);
+      }
+      return;
+    case kLoopHalo:
+      if (k.bn == 128) return launch_halo<128>(a, k.ek, k.Hp, k.Wp, s);
+      return launch_halo<64>(a, k.ek, k.Hp, k.Wp, s);
+    case kLoopRing:
+      if (k.bn == 128) return launch_v2<256, 128, 4, 2>(a, k.ek, s);
+      return launch_v2<256, 64, 4, 2>(a, k.ek, s);
+    case kLoopDma1:
+      if (k.bn == 128) {
+        if (k.mf == 32) return launch_v2<128, 128, 2, 2, 1, 4, 32>(a, k.ek, s);
+        return k.minw == 4 ? launch_v2<128, 128, 2, 2, 1, 4>(a, k.ek, s) : launch_v2<128, 128, 2, 2, 1, 3>(a, k.ek, s);
+      }
+      if (k.mf == 32) return launch_v2<128, 64, 2, 2, 1, 4, 32>(a, k.ek, s);
+      return k.minw == 4 ? launch_v2<128, 64, 2, 2, 1, 4>(a, k.ek, s) : launch_v2<128, 64, 2, 2, 1, 3>(a, k.ek, s);
+    default:
+      if (k.bm == 256) return launch_tile<256, 128>(a, k, s);
+      if (k.bn == 64) return launch_tile<128, 64>(a, k, s);
+      return launch_tile<128, 128>(a, k, s);
+  }
+}
+
+// every kernel select() can name, in a fixed order (the id-to-name table)
+std::vector<Sel> all_sels() {
+  std::vector<Sel> v;
+  const int tiles[3][2] = {{128, 64}, {128, 128}, {256, 128}};
+  for (const auto& t : tiles)
+    for (int d = 0; d < 4; ++d)
+      for (int ek = 0; ek < 4; ++ek)
+        if (igemm_depth(d, ek) == d) v.push_back(Sel{kLoopIgemm, t[0], t[1], d, ek, 16, 0, 0, 0});
+  for (int bn : {64, 128}) v.push_back(Sel{kLoopIgemmInBn, 128, bn, 0, 0, 16, 0, 0, 0});
+  for (int bn : {64, 128})
+    for (int ek = 0; ek < 4; ++ek) v.push_back(Sel{kLoopRing, 256, bn, 0, ek, 16, 0, 0, 0});
+  for (int bn : {64, 128})
+    for (int ek = 0; ek < 4; ++ek) {
+      v.push_back(Sel{kLoopDma1, 128, bn, 0, ek, 32, 4, 0, 0});
+      v.push_back(Sel{kLoopDma1, 128, bn, 0, ek, 16, 4, 0, 0});
+      v.push_back(Sel{kLoopDma1, 128, bn, 0, ek, 16, 3, 0, 0});
+    }
+  for (int bn : {64, 128})
+    for (int ek : {0, 1, 3}) v.push_back(Sel{kLoopHalo, kHaloBM, bn, 0, ek, 32, 0, 0, 0});
+  return v;
 }
 
 }  // namespace
@@ -1216,31 +1311,36 @@ static Igemm dgrad_args(const ConvGeom& g, const void* dy, const void* w_hwio, v
                nullptr, nullptr};
 }
 
-// the row tile launch() picks (the BN partial-sum rows of an epilogue are per row tile)
-int conv_fwd_row_tile(const ConvGeom& g, bool in_bn) {
-  if (in_bn) return 128;
-  {
-    int Hp, Wp;
-    const Igemm a = fwd_args(g, nullptr, nullptr, nullptr);
-    if (use_halo(a, Hp, Wp)) return kHaloBM;
-  }
-  if (use_v2(g.N * g.OH * g.OW, g.K, g.KH * g.KW * (g.C / BK), g.KH * g.KW)) return 256;
-  return (g_forced_tile == 3 && g.K % 128 == 0) ? 256 : 128;
+// a 1x1 stride-1 "convolution" of dy [N][OH][OW][K] with the HWIO rows [C][K] (columns C, reduction K),
+// scattered to the even pixels of dx [N][H][W][C]
+static Igemm dgrad_s2_args(const ConvGeom& g, const void* dy, const void* w_hwio, void* dx) {
+  return Igemm{static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w_hwio), static_cast<uint16_t*>(dx),
+               g.N, g.OH, g.OW, g.K, g.OH, g.OW, g.C, 1, 1, 1, 1, 0, 0, 0,
+               (long long)g.K, 0, 0, g.N * g.OH * g.OW, 2, g.H, g.W, nullptr, nullptr};
 }
 
-int conv_dgrad_row_tile(const ConvGeom& g) {
-  {
-    int Hp, Wp;
-    const Igemm a = dgrad_args(g, nullptr, nullptr, nullptr);
-    if (use_halo(a, Hp, Wp)) return kHaloBM;
-  }
-  if (use_v2(g.N * g.H * g.W, g.C, g.KH * g.KW * (g.K / BK), g.KH * g.KW)) return 256;
-  return (g_forced_tile == 3 && g.C % 128 == 0) ? 256 : 128;
+// the row tile launch() picks (the BN partial-sum rows of an epilogue are per row tile): select()'s
+int conv_fwd_row_tile(const ConvGeom& g, bool in_bn) { return conv_selected(0, g, false, false, in_bn).row_tile; }
+int conv_dgrad_row_tile(const ConvGeom& g) { return conv_selected(1, g, false, false, false).row_tile; }
+int conv_dgrad_s2_row_tile(const ConvGeom& g) { return conv_selected(2, g, false, false, false).row_tile; }
+
+ConvSelected conv_selected(int direction, const ConvGeom& g, bool bn, bool bn_ss, bool in_bn) {
+  // select() only asks whether an optional operand is present: stand-ins that are never dereferenced
+  static float present[1];
+  Igemm a = direction == 0 ? fwd_args(g, nullptr, nullptr, nullptr)
+                           : (direction == 1 ? dgrad_args(g, nullptr, nullptr, nullptr)
+                                             : dgrad_s2_args(g, nullptr, nullptr, nullptr));
+  if (direction != 0 && (bn || bn_ss)) a.bn_part = present;
+  if (direction != 0 && bn_ss) a.bn_ss = present;
+  if (direction == 0 && in_bn) a.in_ss = present;
+  const Sel k = select(a);
+  return ConvSelected{sel_name(k), k.bm};
 }
 
-int conv_dgrad_s2_row_tile(const ConvGeom& g) {
-  if (use_v2(g.N * g.OH * g.OW, g.C, g.K / BK, 1)) return 256;
-  return (g_forced_tile == 3 && g.C % 128 == 0) ? 256 : 128;
+std::vector<std::string> conv_kernel_names() {
+  std::vector<std::string> names;
+  for (const Sel& k : all_sels()) names.push_back(sel_name(k));
+  return names;
 }
 
 void conv_fwd_bf16(const void* x, const void* w_ohwi, void* y, const ConvGeom& g, hipStream_t s, float* stats,
@@ -1270,13 +1370,14 @@ void conv_dgrad_bf16(const void* dy, const void* w_hwio, void* dx, const ConvGeo
 void conv_dgrad_s2_1x1_bf16(const void* dy, const void* w_hwio, void* dx, const ConvGeom& g, hipStream_t s,
                             const void* residual, const void* bn_y, const void* bn_x, float* bn_part,
                             const void* bn_x2, float* bn_part2, const float* bn_ss) {
-  // a 1x1 stride-1 "convolution" of dy [N][OH][OW][K] with the HWIO rows [C][K] (columns C, reduction K),
-  // scattered to the even pixels of dx [N][H][W][C]
-  Igemm a{static_cast<const uint16_t*>(dy), static_cast<const uint16_t*>(w_hwio), static_cast<uint16_t*>(dx),
-          g.N, g.OH, g.OW, g.K, g.OH, g.OW, g.C, 1, 1, 1, 1, 0, 0, 0,
-          (long long)g.K, 0, 0, g.N * g.OH * g.OW, 2, g.H, g.W, static_cast<const uint16_t*>(residual), nullptr,
-          static_cast<const uint16_t*>(bn_y), static_cast<const uint16_t*>(bn_x), bn_part,
-          static_cast<const uint16_t*>(bn_x2), bn_part2, bn_ss};
+  Igemm a = dgrad_s2_args(g, dy, w_hwio, dx);
+  a.res = static_cast<const uint16_t*>(residual);
+  a.bn_y = static_cast<const uint16_t*>(bn_y);
+  a.bn_x = static_cast<const uint16_t*>(bn_x);
+  a.bn_part = bn_part;
+  a.bn_x2 = static_cast<const uint16_t*>(bn_x2);
+  a.bn_part2 = bn_part2;
+  a.bn_ss = bn_ss;
   launch(a, s);
 }
 

@@ -121,6 +121,9 @@ __global__ __launch_bounds__(256, 1) void k_wgrad3x3_c64(W3 a) {
 #pragma unroll
     for (int kk = 0; kk < kMaxOW; kk += 32) {
       if (kk >= OW) break;  // workgroup-uniform
+      // (the step's pixels past OW have dy = 0 and, but for one, x = 0: under tap kw = 0 the pixel OW reads
+      // x's last column.  0 * x is 0 for finite x; a NaN / Inf there also turns the (kh, 0, c, :) entries
+      // of its row's taps into NaN when OW % 32 != 0 -- the gradient is non-finite either way, through kw = 1)
       const int p0 = kk + 8 * (lane >> 4);  // this lane group's 8 output pixels
       bf16x8 fd[4];
 #pragma unroll

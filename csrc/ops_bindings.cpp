@@ -415,12 +415,28 @@ std::vector<at::Tensor> maxpool_bwd_bn(at::Tensor dy, at::Tensor arg, std::vecto
   return {dx, part};
 }
 
+// The output size must be one the input, filter, stride and top / left padding can produce: the bottom /
+// right padding (OH-1)*SH + KH - H - PT that (OH, OW) imply is below the filter size (a larger output
+// would read rows no padding explains; the kernels' range checks would hand it zeros, silently).  It may
+// be negative: the last rows / columns of the input are then unused (stride 2 on an even size).
+// exact (the stride-1 input gradient): the implied padding is also >= 0, every input row is reached.
+void conv_geom_consistent(const tdl::ConvGeom& g, const char* what, bool exact = false) {
+  TORCH_CHECK(g.SH >= 1 && g.SW >= 1 && g.H >= 1 && g.W >= 1, what, ": strides and image sizes must be positive");
+  const int64_t pb = (int64_t)(g.OH - 1) * g.SH + g.KH - g.H - g.PT, pr = (int64_t)(g.OW - 1) * g.SW + g.KW - g.W - g.PL;
+  TORCH_CHECK(pb < g.KH && pr < g.KW, what, ": output ", g.OH, "x", g.OW, " is larger than input ", g.H, "x", g.W,
+              ", filter ", g.KH, "x", g.KW, ", stride ", g.SH, "x", g.SW, " and padding (", g.PT, ", ", g.PL,
+              ") allow (implied bottom / right padding ", pb, ", ", pr, ")");
+  TORCH_CHECK(!exact || (pb >= 0 && pr >= 0), what, ": (h, w) = (", g.H, ", ", g.W, ") does not give dy's ", g.OH, "x",
+              g.OW, " (implied bottom / right padding ", pb, ", ", pr, ")");
+}
+
 tdl::ConvGeom conv_geom(const at::Tensor& x, int64_t oh, int64_t ow, int64_t k, int64_t kh, int64_t kw, int64_t sh,
                         int64_t sw, int64_t pt, int64_t pl) {
   TORCH_CHECK(x.dim() == 4, "conv: NHWC activations expected");
   tdl::ConvGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)oh, (int)ow, (int)k,
                   (int)kh, (int)kw, (int)sh, (int)sw, (int)pt, (int)pl};
   TORCH_CHECK(tdl::conv_bf16_supported(g), "conv: unsupported geometry (C and K must be multiples of 64)");
+  conv_geom_consistent(g, "conv");
   return g;
 }
 
@@ -540,10 +556,12 @@ std::vector<at::Tensor> conv_dgrad_impl(at::Tensor dy, at::Tensor w_hwio, int64_
                                         c10::optional<at::Tensor> bn_x2, c10::optional<at::Tensor> bn_stats) {
   conv_check(dy, "dy");
   conv_check(w_hwio, "w");
+  TORCH_CHECK(dy.dim() == 4, "conv_dgrad: dy must be NHWC [N,OH,OW,K]");
   TORCH_CHECK(w_hwio.dim() == 4 && w_hwio.size(3) == dy.size(3), "conv_dgrad: weights must be HWIO [KH,KW,C,K]");
   tdl::ConvGeom g{(int)dy.size(0), (int)h, (int)w, (int)w_hwio.size(2), (int)dy.size(1), (int)dy.size(2),
                   (int)dy.size(3), (int)w_hwio.size(0), (int)w_hwio.size(1), 1, 1, (int)pt, (int)pl};
   TORCH_CHECK(tdl::conv_bf16_supported(g), "conv_dgrad: unsupported geometry (C and K must be multiples of 64)");
+  conv_geom_consistent(g, "conv_dgrad", true);
   auto dx = fresh({dy.size(0), h, w, w_hwio.size(2)}, dy.options(), 2);
   const int64_t M = (int64_t)g.N * g.H * g.W, bm = tdl::conv_dgrad_row_tile(g);
   DgradBn bn(bn_y, bn_x, bn_x2, bn_stats, dy, h, w, w_hwio.size(2), (M + bm - 1) / bm);
@@ -560,6 +578,7 @@ std::vector<at::Tensor> conv_dgrad_s2_impl(at::Tensor dy, at::Tensor w_hwio, int
                                            c10::optional<at::Tensor> bn_stats) {
   conv_check(dy, "dy");
   conv_check(w_hwio, "w");
+  TORCH_CHECK(dy.dim() == 4, "conv_dgrad_s2: dy must be NHWC [N,OH,OW,K]");
   TORCH_CHECK(w_hwio.dim() == 4 && w_hwio.size(0) == 1 && w_hwio.size(1) == 1 && w_hwio.size(3) == dy.size(3),
               "conv_dgrad_s2: weights must be HWIO [1,1,C,K]");
   TORCH_CHECK(h <= 2 * dy.size(1) && w <= 2 * dy.size(2) && h > 2 * (dy.size(1) - 1) && w > 2 * (dy.size(2) - 1),
@@ -599,6 +618,8 @@ at::Tensor conv_wgrad(at::Tensor x, at::Tensor dy, int64_t kh, int64_t kw, int64
   const float* ss = conv_in_bn(in_bn, g);
   TORCH_CHECK(!ss || plan.empty() || (plan[0] != 0 && plan[0] * plan[1] <= 4 && (plan.size() == 3 || plan[3] == 0)),
               "conv_wgrad: the input-side batch norm runs on the register-staged plans (<= 4 waves, kind 0)");
+  // (a smaller output is a legal 1x1 geometry, but the input-side BN staging reads pixel m of x for row m of dy)
+  TORCH_CHECK(!ss || (g.H == g.OH && g.W == g.OW), "conv_wgrad: the input-side batch norm needs dy as large as x");
   TORCH_CHECK(tdl::conv_wgrad_supported(g), "conv_wgrad: N*OH*OW must be < 2^24");
   TORCH_CHECK(plan.empty() || plan.size() == 3 || plan.size() == 4, "conv_wgrad: plan = [wmw, wnw, nsplit(, kind)]");
   if (!plan.empty() && plan[0] == 0) {  // [0, 0, 0]: the row kernel of 3x3 / C = 64 convs (wgrad3x3.hip)
@@ -724,6 +745,43 @@ std::vector<std::vector<int64_t>> conv_wgrad_plans(std::vector<int64_t> x_shape,
     out.push_back({p.wmw, p.wnw, p.chunk, p.nsplit, p.kind});
   return out;
 }
+// (kernel name, row tile) the launch of one conv geometry takes under the current A/B hooks (conv.h
+// conv_selected; no GPU needed).  direction "fwd" | "dgrad" | "dgrad_s2"; x_shape [N,H,W,C] the conv's
+// input (dx of a gradient), w_shape the direction's own weight layout (OHWI forward, HWIO gradients),
+// (oh, ow) the conv's output size, strides and top / left padding the conv's.  flags: "stats", "residual"
+// (neither moves the selection), "bn" (BN-group backward), "bn_ss" (its mask from bn_stats), "in_bn".
+std::tuple<std::string, int64_t> conv_selected(const std::string& direction, std::vector<int64_t> x_shape,
+                                               std::vector<int64_t> w_shape, int64_t oh, int64_t ow, int64_t sh,
+                                               int64_t sw, int64_t pt, int64_t pl, std::vector<std::string> flags) {
+  const int dir = direction == "fwd" ? 0 : (direction == "dgrad" ? 1 : (direction == "dgrad_s2" ? 2 : -1));
+  TORCH_CHECK(dir >= 0, "conv_selected: direction must be fwd, dgrad or dgrad_s2");
+  TORCH_CHECK(x_shape.size() == 4 && w_shape.size() == 4, "conv_selected: x_shape [N,H,W,C] and a 4-D w_shape expected");
+  bool bn = false, bn_ss = false, in_bn = false;
+  for (const auto& f : flags) {
+    TORCH_CHECK(f == "stats" || f == "residual" || f == "bn" || f == "bn_ss" || f == "in_bn",
+                "conv_selected: unknown flag ", f);
+    bn = bn || f == "bn";
+    bn_ss = bn_ss || f == "bn_ss";
+    in_bn = in_bn || f == "in_bn";
+  }
+  const int64_t k = dir == 0 ? w_shape[0] : w_shape[3], kh = dir == 0 ? w_shape[1] : w_shape[0],
+                kw = dir == 0 ? w_shape[2] : w_shape[1], c = dir == 0 ? w_shape[3] : w_shape[2];
+  TORCH_CHECK(c == x_shape[3], "conv_selected: the weights' input channels must match x_shape");
+  TORCH_CHECK(dir == 0 || !in_bn, "conv_selected: in_bn is a forward flag");
+  TORCH_CHECK(dir != 0 || !(bn || bn_ss), "conv_selected: bn / bn_ss are input-gradient flags");
+  tdl::ConvGeom g{(int)x_shape[0], (int)x_shape[1], (int)x_shape[2], (int)c, (int)oh, (int)ow, (int)k,
+                  (int)kh, (int)kw, (int)sh, (int)sw, (int)pt, (int)pl};
+  TORCH_CHECK(dir != 1 || (sh == 1 && sw == 1), "conv_selected: dgrad is the stride-1 input gradient");
+  TORCH_CHECK(dir != 2 || (sh == 2 && sw == 2 && kh == 1 && kw == 1 && pt == 0 && pl == 0),
+              "conv_selected: dgrad_s2 is the input gradient of a 1x1 stride-2 unpadded conv");
+  TORCH_CHECK(tdl::conv_bf16_supported(g), "conv_selected: unsupported geometry (C and K must be multiples of 64)");
+  conv_geom_consistent(g, "conv_selected", dir == 1);
+  TORCH_CHECK(!in_bn || tdl::conv_in_bn_supported(g),
+              "conv_selected: the input-side batch norm takes 1x1 stride-1 unpadded convolutions of <= 512 channels");
+  const auto r = tdl::conv_selected(dir, g, bn || bn_ss, bn_ss, in_bn);
+  return {r.name, (int64_t)r.row_tile};
+}
+
 // dst (bf16 slab) <- transposed copies of the HWIO f32 conv kernels in src (f32 slab); entries
 // [E][4] (src off, dst off, R, K) and tiles [T][4] (entry, row tile, col tile, 0) int32 on the GPU
 void slab_transpose_bf16(at::Tensor src, at::Tensor dst, at::Tensor entries, at::Tensor tiles) {
@@ -1203,6 +1261,12 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("x_shape"), pybind11::arg("dy_shape"), pybind11::arg("kh"), pybind11::arg("kw"),
         pybind11::arg("sh"), pybind11::arg("sw"), pybind11::arg("pt"), pybind11::arg("pl"), pybind11::arg("max_plans"),
         pybind11::arg("in_bn") = false);
+  m.def("conv_selected", &conv_selected,
+        "(kernel name, row tile) a conv launch of this geometry takes under the current hooks; no GPU needed",
+        pybind11::arg("direction"), pybind11::arg("x_shape"), pybind11::arg("w_shape"), pybind11::arg("oh"),
+        pybind11::arg("ow"), pybind11::arg("sh") = 1, pybind11::arg("sw") = 1, pybind11::arg("pt") = 0,
+        pybind11::arg("pl") = 0, pybind11::arg("flags") = std::vector<std::string>{});
+  m.def("conv_kernel_names", &tdl::conv_kernel_names, "every kernel name conv_selected can return");
   m.def("conv_force_tile", &tdl::conv_force_tile, "conv tile sweep hook (0 = heuristic)");
   m.def("conv_force_impl", &tdl::conv_force_impl,
         "conv main loop A/B hook: 1 v1 register staged, 2 default selection, 3 LDS-DMA ring, 4/5 dma1 at 4/3 waves "

@@ -1,0 +1,168 @@
+"""tests/conv_refs.py against torch.nn.functional.conv2d / torch.nn.grad in float64 on the CPU: random
+geometries (strides, rectangular filters, asymmetric padding built with F.pad, outputs that leave the last
+input rows unused), and the epilogue references on hand-checked values.  No GPU."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import conv_refs as CR
+import kernel_refs as R
+
+
+def _geoms():
+    rng = np.random.RandomState(7)
+    out = [(1, 1, 1, 2, 3, 1, 1, 1, 1, 0, 0, 0, 0),  # M = 1
+           (2, 2, 5, 3, 2, 3, 3, 1, 1, 2, 2, 2, 2),  # H < KH, PT = KH - 1
+           (2, 6, 6, 2, 3, 3, 3, 2, 2, 0, 1, 0, 1),  # stride 2 'same' on an even size: top 0, bottom 1
+           (1, 7, 5, 2, 2, 1, 7, 1, 1, 0, 0, 3, 3), (1, 7, 5, 2, 2, 7, 1, 1, 1, 3, 3, 0, 0),
+           (1, 6, 9, 2, 2, 4, 8, 1, 1, 1, 2, 3, 4), (2, 5, 5, 3, 2, 2, 2, 1, 1, 1, 0, 0, 1)]
+    while len(out) < 40:
+        N, H, W, C, K = rng.randint(1, 3), rng.randint(1, 9), rng.randint(1, 9), rng.randint(1, 4), rng.randint(1, 4)
+        KH, KW, SH, SW = rng.randint(1, 5), rng.randint(1, 5), rng.randint(1, 3), rng.randint(1, 3)
+        pt, pl = rng.randint(0, KH), rng.randint(0, KW)
+        pb, pr = rng.randint(0, KH), rng.randint(0, KW)
+        if H + pt + pb < KH or W + pl + pr < KW:
+            continue
+        out.append((N, H, W, C, K, KH, KW, SH, SW, pt, pb, pl, pr))
+    return out
+
+
+def _torch_case(g):
+    N, H, W, C, K, KH, KW, SH, SW, pt, pb, pl, pr = g
+    rng = np.random.RandomState(sum(g))
+    x = rng.randn(N, H, W, C)
+    w = rng.randn(KH, KW, C, K)  # HWIO
+    xt = torch.tensor(x).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    wt = torch.tensor(w).permute(3, 2, 0, 1).contiguous().requires_grad_(True)
+    y = F.conv2d(F.pad(xt, (pl, pr, pt, pb)), wt, None, (SH, SW))
+    return x, w, xt, wt, y
+
+
+@pytest.mark.parametrize("g", _geoms())
+def test_convolutions_match_torch_float64(g):
+    N, H, W, C, K, KH, KW, SH, SW, pt, pb, pl, pr = g
+    x, w, xt, wt, y = _torch_case(g)
+    OH, OW = y.shape[2], y.shape[3]
+    got, ab = CR.conv_fwd_ref(x, w.transpose(3, 0, 1, 2), OH, OW, SH, SW, pt, pl)
+    np.testing.assert_allclose(got, y.detach().permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    want_ab = F.conv2d(F.pad(xt.detach().abs(), (pl, pr, pt, pb)), wt.detach().abs(), None, (SH, SW))
+    np.testing.assert_allclose(ab, want_ab.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    dy = np.random.RandomState(1).randn(N, OH, OW, K)
+    y.backward(torch.tensor(dy).permute(0, 3, 1, 2))
+    dx, _ = CR.conv_dgrad_ref(dy, w, H, W, SH, SW, pt, pl)
+    np.testing.assert_allclose(dx, xt.grad.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    dw, _ = CR.conv_wgrad_ref(x, dy, KH, KW, SH, SW, pt, pl)
+    np.testing.assert_allclose(dw, wt.grad.permute(2, 3, 1, 0).numpy(), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("hw", [(4, 4), (5, 4), (4, 5), (5, 5), (1, 1)])
+def test_stride2_gradient_matches_torch_nn_grad(hw):
+    H, W = hw
+    OH, OW = (H + 1) // 2, (W + 1) // 2
+    rng = np.random.RandomState(3)
+    dy, w = rng.randn(2, OH, OW, 3), rng.randn(1, 1, 4, 3)
+    want = torch.nn.grad.conv2d_input((2, 4, H, W), torch.tensor(w).permute(3, 2, 0, 1),
+                                      torch.tensor(dy).permute(0, 3, 1, 2), stride=2)
+    got, _ = CR.conv_dgrad_s2_ref(dy, w, H, W)
+    np.testing.assert_allclose(got, want.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    assert np.all(got[:, 1::2] == 0) and np.all(got[:, :, 1::2] == 0)
+
+
+def test_unreached_rows_are_ignored():
+    """Stride 2, 3x3, H = 6 unpadded: OH = 2 reads rows 0..4; row 5 takes no part in y and gets no gradient."""
+    rng = np.random.RandomState(0)
+    x, w = rng.randn(1, 6, 6, 2), rng.randn(3, 3, 3, 2)
+    y, _ = CR.conv_fwd_ref(x, w, 2, 2, 2, 2, 0, 0)
+    x2 = x.copy()
+    x2[:, 5] = 99.0
+    x2[:, :, 5] = -99.0
+    assert np.array_equal(CR.conv_fwd_ref(x2, w, 2, 2, 2, 2, 0, 0)[0], y)
+    dx, _ = CR.conv_dgrad_ref(y, w.transpose(1, 2, 3, 0), 6, 6, 2, 2, 0, 0)
+    assert np.all(dx[:, 5] == 0) and np.all(dx[:, :, 5] == 0) and np.all(dx[:, :5, :5] != 0)
+
+
+def _bits(v):
+    return R.bf16_rne(np.asarray(v, np.float32))
+
+
+def test_rounding_order_and_ties():
+    # 257 is halfway between 256 and 258: to even (256); 259 between 258 and 260: to even (260)
+    assert list(R.bf16_bits_to_f64(CR.round_bf16([257.0, 259.0, -257.0, -259.0]))) == [256.0, 260.0, -256.0, -260.0]
+    assert CR.count_ties(np.array([257.0, 259.0, -259.0, 256.0, 3.0, 0.0])) == (1, 2, 1, 2)
+    # bf16(bf16(acc) + res) rounds twice: 257 -> 256, + 1 = 257 -> 256; one rounding of 258 would give 258
+    assert R.bf16_bits_to_f64(CR.add_residual(CR.round_bf16([257.0]), _bits([1.0])))[0] == 256.0
+    # halfway to Inf rounds to Inf; just below stays finite
+    top = 2.0 ** 127 + 255 * 2.0 ** 119
+    assert CR.round_bf16([top])[0] == 0x7F80 and CR.round_bf16([-top])[0] == 0xFF80
+    assert CR.round_bf16([np.float32(top) - np.float32(2.0 ** 104)])[0] == 0x7F7F
+    for nan in (0x7FFF, 0xFFFF, 0x7F81):
+        assert R.bf16_is_nan(CR.add_residual(_bits([3.0]), np.array([nan], np.uint16)))[0]
+
+
+def test_masks_follow_the_bit_rule():
+    by = np.array([0x0000, 0x8000, 0x0001, 0x8001, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0, 0x3F80, 0xBF80], np.uint16)
+    assert list(CR.mask_from_bits(by)) == [False, False, True, False, True, False, True, False, True, False]
+    one = np.float32(1.0)
+    # x * 2 - 6 at x = 3 is exactly 0 (masked); one ulp of the shift either side decides
+    bx = _bits([3.0, 3.0, 3.0, np.nan])
+    sh = np.array([-6.0, np.nextafter(np.float32(-6), np.float32(0)), np.nextafter(np.float32(-6), np.float32(-7)),
+                   1.0], np.float32)
+    assert list(CR.mask_from_stats(bx, np.array([2.0, 2.0, 2.0, 1.0], np.float32) * one, sh)) == [False, True, False, False]
+    assert list(R.bf16_bits_to_f64(CR.in_bn_ref(_bits([3.0, -3.0, np.nan]), np.float32([2, 2, 1]), np.float32([1, 1, 1])))) == [7.0, 0.0, 0.0]
+
+
+def test_tile_sums_use_the_stored_values_and_count_tail_rows_only():
+    v = np.zeros((130, 2))
+    v[:, 0] = 257.0  # stored as 256
+    v[129, 1] = 3.0
+    s = CR.tile_sums(CR.round_bf16(v), None, 128)
+    assert s.shape == (2, 2, 2)
+    assert s[0, 0, 0] == 128 * 256 and s[0, 1, 0] == 128 * 256 ** 2 and s[1, 0, 0] == 2 * 256
+    assert s[1, 0, 1] == 3 and s[1, 1, 1] == 9 and s[0, 0, 1] == 0
+    assert CR.part_rows(1) == 2 and CR.part_rows(64) == 65 and CR.part_rows(65) == 67
+    with pytest.raises(AssertionError):
+        CR.tile_sums(CR.round_bf16(np.full((128, 1), 512.0)), None, 128)  # 128 * 512^2 = 2^25
+
+
+@pytest.mark.parametrize("hw", [(4, 4), (5, 3), (3, 6)])
+def test_stride2_epilogue_covers_all_four_pixels(hw):
+    H, W = hw
+    OH, OW = (H + 1) // 2, (W + 1) // 2
+    rng = np.random.RandomState(5)
+    acc = rng.randint(-300, 300, (2, OH, OW, 2)).astype(np.float64)
+    res = rng.randint(-5, 6, (2, H, W, 2)).astype(np.float64)
+    by = rng.randint(-1, 2, (2, H, W, 2)).astype(np.float64)
+    bx = rng.randint(-3, 4, (2, H, W, 2)).astype(np.float64)
+    dz, part, part2 = CR.dgrad_s2_epilogue_ref(acc, H, W, 3, _bits(res), _bits(by), _bits(bx), None, _bits(by))
+    want = res.copy()
+    want[:, ::2, ::2] = R.bf16_bits_to_f64(CR.round_bf16(acc)) + res[:, ::2, ::2]
+    want = R.bf16_bits_to_f64(_bits(want)) * (by > 0)
+    assert np.array_equal(R.bf16_bits_to_f64(dz), want)
+    assert part.shape == ((2 * OH * OW + 2) // 3, 2, 2)
+    np.testing.assert_array_equal(part.sum(0)[0], want.sum((0, 1, 2)))
+    np.testing.assert_array_equal(part.sum(0)[1], (want * bx).sum((0, 1, 2)))
+    np.testing.assert_array_equal(part2.sum(0)[1], (want * by).sum((0, 1, 2)))
+    # the first tile: dy pixels 0..2 of image 0 and their blocks
+    blocks = [(0, i // OW, i % OW) for i in range(3)] if OH * OW >= 3 else None
+    if blocks:
+        t = sum(want[n, 2 * i:2 * i + 2, 2 * j:2 * j + 2].sum((0, 1)) for n, i, j in blocks)
+        np.testing.assert_array_equal(part[0, 0], t)
+
+
+def test_coded_data_is_position_coded_and_bounded():
+    a = CR.coded_ints((2, 5, 6, 64), 9, 1)
+    assert a.min() >= -9 and a.max() <= 9 and np.all(a == np.round(a))
+    assert not np.array_equal(a[:, 1:], a[:, :-1]) and not np.array_equal(a[:, ::-1], a)
+    assert not np.array_equal(a, CR.coded_ints((2, 5, 6, 64), 9, 2))
+    z = CR.coded_ints((4, 8, 8, 64), 9, 1, zero_frac=0.9)
+    assert 0.8 < (z == 0).mean() < 0.97
+    assert CR.amp_for(64, 350) >= 8 and CR.amp_for(4608, 350) <= 4
+
+
+def test_error_bound_is_the_derived_one():
+    r, ab = np.array([1.0, 300.0]), np.array([10.0, 4000.0])
+    e = 576 * 2.0 ** -23 * ab
+    np.testing.assert_array_equal(CR.error_bound(r, ab, 576), 0.5 * R.ulp_bf16(np.abs(r) + e) + e)
+    with pytest.raises(AssertionError):
+        CR.assert_exact(np.array([2.0 ** 24]))

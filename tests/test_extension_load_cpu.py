@@ -17,7 +17,7 @@ def test_hip_extension_imports_with_every_entry_point():
 
     C = hip()
     for name in ("conv_fwd", "conv_fwd_stats", "conv_dgrad", "conv_dgrad_bn", "conv_dgrad_s2", "conv_wgrad",
-                 "conv_wgrad_plans", "conv_force_impl", "bn_forward_train", "bn_backward", "gemm_bf16", "MnistStep",
+                 "conv_wgrad_plans", "conv_force_impl", "conv_selected", "conv_kernel_names", "bn_forward_train", "bn_backward", "gemm_bf16", "MnistStep",
                  "XgmiChannel", "stem_fwd", "maxpool_fwd"):
         assert hasattr(C, name), name
 
