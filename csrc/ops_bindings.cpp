@@ -8,6 +8,7 @@
 
 #include "kernels/bn.h"
 #include "kernels/conv.h"
+#include "kernels/dropout.h"
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/ops.h"
@@ -387,6 +388,86 @@ at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor arg, std::vector<int64_t> in_sh
   tdl::maxpool_backward(dy.data_ptr(), arg.data_ptr<uint8_t>(), dx.data_ptr(), bn_dtype(dy) == tdl::BnDType::kBF16, g,
                         cur_stream());
   return dx;
+}
+
+// ---- seeded dropout (csrc/kernels/dropout.hip; the stream and the ticket protocol: kernels/dropout.h) ----
+// noise_strides: per dimension of x, the stride of that coordinate in the mask's index space (0 where the
+// mask is broadcast); absent = the mask has x's shape.  Adjacent dimensions that form one run of the mask
+// index are merged, and what remains must fit 4 dimensions.
+at::Tensor dropout_run(const at::Tensor& x, int64_t* state, const int64_t* ticket_in, int64_t* ticket_out, int64_t k0,
+                       int64_t k1, int64_t T, double scale, const c10::optional<std::vector<int64_t>>& noise_strides,
+                       int64_t elem_offset) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(), "dropout: contiguous GPU tensor expected");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, "dropout: float32 or bfloat16 expected");
+  TORCH_CHECK(k0 >= 0 && k0 <= 0xffffffffLL && k1 >= 0 && k1 <= 0xffffffffLL, "dropout: key words are 32-bit");
+  TORCH_CHECK(T >= 0 && T <= (1LL << 32), "dropout: threshold must be in [0, 2^32]");
+  TORCH_CHECK(elem_offset >= 0 && elem_offset % 4 == 0, "dropout: elem_offset must be a non-negative multiple of 4");
+  auto y = at::empty_like(x);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(y.data_ptr()) % 16 == 0,
+              "dropout: 16-byte aligned data expected");
+  tdl::DropoutArgs a;
+  a.x = x.data_ptr();
+  a.y = y.data_ptr();
+  a.n = x.numel();
+  a.state = state;
+  a.ticket_in = ticket_in;
+  a.ticket_out = ticket_out;
+  a.k0 = (uint32_t)k0;
+  a.k1 = (uint32_t)k1;
+  a.thr = (uint64_t)T;
+  a.scale = (float)scale;
+  a.elem_offset = elem_offset;
+  a.bf16 = x.scalar_type() == at::kBFloat16;
+  if (!noise_strides.has_value()) {
+    tdl::dropout_apply(a, cur_stream());
+    return y;
+  }
+  const auto& ns = *noise_strides;
+  TORCH_CHECK((int64_t)ns.size() == x.dim(), "dropout: one noise stride per dimension expected");
+  std::vector<int64_t> d, st;
+  for (int64_t k = 0; k < x.dim(); ++k) {
+    TORCH_CHECK(ns[k] >= 0, "dropout: negative noise stride");
+    if (x.size(k) == 1) continue;
+    if (!d.empty() && st.back() == ns[k] * x.size(k)) {  // one run of the mask index: merge
+      d.back() *= x.size(k);
+      st.back() = ns[k];
+    } else {
+      d.push_back(x.size(k));
+      st.push_back(ns[k]);
+    }
+  }
+  if (d.empty() || (d.size() == 1 && st[0] == 1)) {  // the mask index is the element index
+    tdl::dropout_apply(a, cur_stream());
+    return y;
+  }
+  TORCH_CHECK(d.size() <= 4, "dropout: noise_shape needs more than 4 dimensions after merging");
+  int64_t dims[4] = {1, 1, 1, 1}, nst[4] = {0, 0, 0, 0};
+  const size_t pad = 4 - d.size();
+  for (size_t k = 0; k < d.size(); ++k) {
+    dims[pad + k] = d[k];
+    nst[pad + k] = st[k];
+  }
+  tdl::dropout_apply_bcast(a, dims, nst, cur_stream());
+  return y;
+}
+
+std::vector<at::Tensor> dropout_fwd(at::Tensor x, at::Tensor state, int64_t k0, int64_t k1, int64_t T, double scale,
+                                    c10::optional<std::vector<int64_t>> noise_strides, int64_t elem_offset) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.numel() == 2 && state.is_contiguous() &&
+                  state.device() == x.device(),
+              "dropout: state must be an int64 [calls, arrivals] tensor on x's device");
+  auto ticket = at::empty({1}, state.options());
+  auto y = dropout_run(x, state.data_ptr<int64_t>(), nullptr, ticket.data_ptr<int64_t>(), k0, k1, T, scale,
+                       noise_strides, elem_offset);
+  return {y, ticket};
+}
+
+at::Tensor dropout_bwd(at::Tensor dy, at::Tensor ticket, int64_t k0, int64_t k1, int64_t T, double scale,
+                       c10::optional<std::vector<int64_t>> noise_strides, int64_t elem_offset) {
+  TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 1 &&
+                  ticket.device() == dy.device(),
+              "dropout: ticket must be the forward's 1-element int64 tensor");
+  return dropout_run(dy, nullptr, ticket.data_ptr<int64_t>(), nullptr, k0, k1, T, scale, noise_strides, elem_offset);
 }
 
 // backward of maxpool_fwd(bn_stats=...): (dz, part) -- dz the BN -> ReLU group's masked input gradient,
@@ -1278,6 +1359,17 @@ void register_ops(pybind11::module& m) {
   m.def("conv_wgrad3x3_set_rows", &tdl::conv_wgrad3x3_set_rows, "3x3 row-kernel wgrad: output rows per slice (0 = auto)");
   m.def("conv_wgrad_force_single", &tdl::conv_wgrad_force_single,
         "weight-gradient A/B hook: single LDS stage at 3 waves/SIMD (True) or double-buffered (False, default)");
+  m.attr("DROPOUT_WG_ELEMS") = (int64_t)tdl::kDropoutWgElems;  // elements per workgroup and grid-stride trip
+  m.attr("DROPOUT_MAX_GRID") = (int64_t)tdl::kDropoutMaxGrid;  // grid cap of the dropout kernels
+  m.attr("DROPOUT_SMALL_N") = (int64_t)tdl::kDropoutSmallN;    // up to this many elements: ...
+  m.attr("DROPOUT_SMALL_WG_ELEMS") = (int64_t)tdl::kDropoutSmallWgElems;  // ... this many per workgroup and trip
+  m.def("dropout_force_max_grid", &tdl::dropout_force_max_grid, "dropout test hook: grid cap (0 = DROPOUT_MAX_GRID)");
+  m.def("dropout_fwd", &dropout_fwd, "seeded dropout forward: (y, ticket); advances state = [calls, arrivals]",
+        pybind11::arg("x"), pybind11::arg("state"), pybind11::arg("k0"), pybind11::arg("k1"), pybind11::arg("T"),
+        pybind11::arg("scale"), pybind11::arg("noise_strides") = pybind11::none(), pybind11::arg("elem_offset") = 0);
+  m.def("dropout_bwd", &dropout_bwd, "seeded dropout backward: dx from dy and the forward's ticket (mask recomputed)",
+        pybind11::arg("dy"), pybind11::arg("ticket"), pybind11::arg("k0"), pybind11::arg("k1"), pybind11::arg("T"),
+        pybind11::arg("scale"), pybind11::arg("noise_strides") = pybind11::none(), pybind11::arg("elem_offset") = 0);
   m.def("maxpool_force_generic", &tdl::maxpool_force_generic,
         "max-pool A/B hook: generic window loops (True, default) or the unrolled 3x3 stride-2 kernels (False)");
   m.def("maxpool_w2", &tdl::maxpool_w2,

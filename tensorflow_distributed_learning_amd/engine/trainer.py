@@ -160,6 +160,7 @@ class GenericTrainer:
             self._bind_compute_views()
         self._buckets = self._make_buckets()
         self._prepare_sync_bn()
+        self._prepare_dropout()
         self._bind_cast_accumulate()
         # whole-step hipGraphs (forward + backward + all-reduce + optimizer + metrics), keyed by
         # the batch signature; the first two steps of a signature run eagerly (solver search,
@@ -313,6 +314,22 @@ class GenericTrainer:
         self._sync_bn_sizes = [_bn.sync_exchange_numel(comm, c) for c in chans]
         comm.prepare_all_reduce(*self._sync_bn_sizes)
 
+    def _prepare_dropout(self):
+        """Dropout layers keep their call counter in a device tensor that the forward kernel advances
+        (ops/dropout.py): create it now, so that a captured step records no allocation or fill of it."""
+        if self.device.type != "cuda":
+            return
+        from ..keras import layers as L
+
+        def walk(m):
+            for l in getattr(m, "layers", []):
+                yield l
+                yield from walk(l)
+
+        for l in walk(self.model):
+            if isinstance(l, L.Dropout):
+                l._state_for(self.device)
+
     def _register_bucket_hooks(self):
         """Post-accumulate hooks on the CURRENT leaves: the last gradient of a bucket launches that
         bucket's asynchronous all-reduce."""
@@ -351,7 +368,9 @@ class GenericTrainer:
             ctx = torch.autocast("cuda", dtype=torch.bfloat16, cache_enabled=False)
         else:
             ctx = torch.autocast(self.device.type, enabled=False)
-        with ctx:
+        from ..parallel.strategy import _training_replica
+
+        with ctx, _training_replica(self.strategy.extended.rank):
             y_pred = model(x, training=True)
         fused = self._fused_head(y, y_pred, sw)
         if fused is not None:

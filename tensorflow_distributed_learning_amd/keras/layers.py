@@ -26,6 +26,7 @@ from . import activations as _act
 from . import initializers as _init
 
 _UIDS: Dict[str, int] = defaultdict(int)
+_DROPOUT_STREAMS = [0]  # creation index of the next Dropout layer without a seed of its own (its RNG stream)
 
 
 def _snake(name: str) -> str:
@@ -42,6 +43,7 @@ def unique_name(prefix: str) -> str:
 
 def reset_uids():
     _UIDS.clear()
+    _DROPOUT_STREAMS[0] = 0
 
 
 def _pair(v) -> Tuple[int, int]:
@@ -673,16 +675,152 @@ class Softmax(Layer):
         return s
 
 
+def _replica_id() -> int:
+    """The replica whose step the calling thread runs: the id the engine set around its forward pass
+    (one process per GPU: the process rank; replica threads: the thread's replica), else the replica
+    context's (``strategy.run``), else the current strategy's rank; 0 outside a strategy."""
+    from ..parallel import strategy as _st
+
+    r = _st.training_replica()
+    if r is not None:
+        return int(r)
+    ctx = _st.get_replica_context()
+    if ctx is not None:
+        return int(ctx.replica_id_in_sync_group)
+    return int(_st.get_strategy().extended.rank)
+
+
 class Dropout(Layer):
+    """tf.keras.layers.Dropout with a reproducible mask (ops/dropout.py): the mask of a call is a function
+    of (seed, the layer's stream, the replica, the call number) alone, the same bits on the CPU and on the
+    GPU, in eager steps and in replayed graphs, and it is recomputed in the backward instead of saved.
+
+    ``seed``: an explicit seed uses stream 0, so two layers with one seed draw the same masks; ``None`` uses
+    the global seed (``keras.utils.set_random_seed``; unset: ``torch.initial_seed()`` at first use) and the
+    layer's creation index as its stream (``backend.clear_session`` restarts the index).  Replicas draw
+    different masks from the same seed.  ``noise_shape``: per dimension None (or the input's size) or 1; the
+    mask is broadcast along the dimensions given as 1.
+
+    The call number is kept per device: in a small device tensor advanced by the forward kernel on the GPU,
+    in a Python counter on the CPU.  Reusing the layer several times in one step takes consecutive numbers.
+    Concurrent calls of one layer object on two streams of one device are not supported (the two launches
+    would share the counter's arrival word).  ``TDL_DROPOUT=torch`` restores ``F.dropout``."""
+
     def __init__(self, rate, noise_shape=None, seed=None, **kw):
         super().__init__(**kw)
         self.rate = float(rate)
+        if not 0.0 <= self.rate <= 1.0:  # (a NaN rate fails here too)
+            raise ValueError(f"{type(self).__name__}: rate must be in [0, 1], got {rate!r}")
+        if noise_shape is not None:
+            noise_shape = tuple(None if d is None else int(d) for d in noise_shape)
+            if any(d is not None and d < 1 for d in noise_shape):
+                raise ValueError(f"{type(self).__name__}: noise_shape entries must be None or positive, got {noise_shape}")
+        self.noise_shape = noise_shape
+        self.seed = None if seed is None else int(seed)
+        if self.seed is None:
+            self._rng_stream = _DROPOUT_STREAMS[0]
+            _DROPOUT_STREAMS[0] += 1
+        else:
+            self._rng_stream = 0
+        self._rng_state: Dict[torch.device, torch.Tensor] = {}
+        self._cpu_calls = 0
+
+    # ------------------------------------------------------------------ RNG state
+    def _key(self):
+        from ..ops import dropout as _do
+
+        seed = self.seed if self.seed is not None else _do.global_seed()
+        return _do.stream_key(seed, self._rng_stream, _replica_id())
+
+    def _state_for(self, device) -> torch.Tensor:
+        """The device's ``[calls, arrivals]`` tensor, created on first use (outside any graph capture: the
+        engines create it before they capture a step)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._rng_state.get(device)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self.name}: the dropout call counter of {device} must exist before a graph "
+                                   "capture (call the layer once eagerly, or layer._state_for(device))")
+            st = self._rng_state[device] = torch.zeros(2, dtype=torch.int64, device=device)
+        return st
+
+    def reset_rng(self, calls: int = 0):
+        """Restart the call counter at ``calls`` on every device (and on the CPU): the masks replay."""
+        self._cpu_calls = int(calls)
+        for st in self._rng_state.values():
+            st.copy_(torch.tensor([int(calls), 0], dtype=torch.int64))
+
+    def rng_calls(self, device="cpu") -> int:
+        """Calls counted on ``device`` so far (synchronises; for tests and debugging)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            return self._cpu_calls
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._rng_state.get(device)
+        return 0 if st is None else int(st.cpu()[0])
+
+    # ------------------------------------------------------------------ call
+    def _noise_shape_for(self, x):
+        ns = self.noise_shape
+        if ns is None:
+            return None
+        if len(ns) != x.dim():
+            raise ValueError(f"{self.name}: noise_shape {ns} has {len(ns)} entries, the input {x.dim()} dimensions")
+        out = []
+        for d, s in zip(ns, x.shape):
+            if d is None or d == s:
+                out.append(int(s))
+            elif d == 1:
+                out.append(1)
+            else:
+                raise ValueError(f"{self.name}: noise_shape entry {d} is neither 1 nor the input's size {s}")
+        return tuple(out)
 
     def call(self, x, training=None):
-        return F.dropout(x, self.rate, training=bool(training))
+        from ..ops import dropout as _do
+
+        if not training or self.rate == 0.0:
+            return x
+        if _do.use_torch():
+            ns = self._noise_shape_for(x)
+            if ns is None:
+                return F.dropout(x, self.rate, training=True)
+            return x * F.dropout(torch.ones(ns, dtype=x.dtype, device=x.device), self.rate, training=True)
+        ns = self._noise_shape_for(x)
+        if x.is_cuda:
+            return _do.dropout(x, self.rate, self._key(), state=self._state_for(x.device), noise_shape=ns)
+        t = self._cpu_calls
+        self._cpu_calls += 1
+        return _do.dropout(x, self.rate, self._key(), ticket=t, noise_shape=ns)
 
     def compute_output_shape(self, s):
         return s
+
+    def get_config(self):
+        return dict(super().get_config(), rate=self.rate,
+                    noise_shape=list(self.noise_shape) if self.noise_shape is not None else None, seed=self.seed)
+
+
+class SpatialDropout2D(Dropout):
+    """tf.keras.layers.SpatialDropout2D (NHWC): whole feature maps are dropped, the mask is ``(N, 1, 1, C)``."""
+
+    def __init__(self, rate, data_format=None, seed=None, **kw):
+        if data_format not in (None, "channels_last"):
+            raise ValueError("SpatialDropout2D: only channels_last (NHWC) is supported")
+        super().__init__(rate, noise_shape=None, seed=seed, **kw)
+
+    def _noise_shape_for(self, x):
+        if x.dim() != 4:
+            raise ValueError(f"{self.name}: a 4-D NHWC input is expected, got {x.dim()} dimensions")
+        return (int(x.shape[0]), 1, 1, int(x.shape[3]))
+
+    def get_config(self):
+        cfg = super().get_config()
+        cfg.pop("noise_shape", None)
+        return cfg
 
 
 class Rescaling(Layer):
@@ -952,5 +1090,8 @@ def multiply(inputs, **kw):
 
 LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
-    Reshape, Activation, ReLU, Softmax, Dropout, Rescaling, ZeroPadding2D, BatchNormalization, SyncBatchNormalization,
-    LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, Rescaling, ZeroPadding2D, BatchNormalization,
+    SyncBatchNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+
+# the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
+__all__ = sorted(LAYER_CLASSES) + ["Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]

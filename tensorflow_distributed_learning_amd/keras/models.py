@@ -428,6 +428,7 @@ class Model(Layer):
                         m.compile_from_config(self._compile_config)
                         m._bucket_bytes = self._bucket_bytes
                 m._distribution_strategy = view
+                _copy_rng_streams(self, m)
                 clones.append(m)
             self._local_clones = clones
         for m in clones:  # every replica starts from replica 0's current values (mirrored variables)
@@ -913,6 +914,23 @@ class Sequential(Model):
         for l in self._seq:
             s = l.compute_output_shape(s)
         return s
+
+
+def _copy_rng_streams(src, dst):
+    """A replica clone's Dropout layers draw from their originals' streams (the replicas then differ by
+    the replica id in the key alone), not from the creation indices the clone's own layers took."""
+    from .layers import Dropout
+
+    def walk(m):
+        for l in getattr(m, "layers", []):
+            yield l
+            yield from walk(l)
+
+    a = [l for l in walk(src) if isinstance(l, Dropout)]
+    b = [l for l in walk(dst) if isinstance(l, Dropout)]
+    assert len(a) == len(b), "a model clone has other Dropout layers than its original"
+    for la, lb in zip(a, b):
+        lb._rng_stream = la._rng_stream
 
 
 def model_from_config(cfg):

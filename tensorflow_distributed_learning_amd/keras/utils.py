@@ -17,8 +17,10 @@ def to_categorical(y, num_classes=None, dtype="float32"):
 
 def set_random_seed(seed: int):
     from ..data import dataset as D
+    from ..ops import dropout as _dropout
     from . import initializers
 
+    _dropout.set_global_seed(seed)
     random.seed(seed)
     np.random.seed(seed)
     torch.manual_seed(seed)

@@ -149,6 +149,23 @@ def _replica(ctx):
         _state.replica_ctx = prev
 
 
+def training_replica() -> Optional[int]:
+    """The replica id an engine set around its forward pass on this thread (:func:`_training_replica`), else
+    None.  A training step runs in cross-replica context (the engine issues the collectives itself), so
+    layers that need their replica's index (keras/layers.py Dropout) read it here."""
+    return getattr(_state, "training_replica", None)
+
+
+@contextlib.contextmanager
+def _training_replica(rank: int):
+    prev = getattr(_state, "training_replica", None)
+    _state.training_replica = int(rank)
+    try:
+        yield
+    finally:
+        _state.training_replica = prev
+
+
 @contextlib.contextmanager
 def _cross_replica():
     prev = getattr(_state, "replica_ctx", None)
