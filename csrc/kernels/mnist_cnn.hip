@@ -739,12 +739,19 @@ constexpr int kLdsFwd = 784 + 320 + 169 * kP1Stride + 72 * 16 * 4 + 400 + 169 * 
 // distinct 4-bank groups; the 4 consecutive cells of a wgrad B read (ds_read_b32) on 4 x 16 banks.
 constexpr int kDcF = 15, kDcFStride = 20;
 constexpr int kLdsFwdFused = kLdsFwd + kDcF * kDcF * kDcFStride;
+// The live part of the pooled conv1 output: conv2 outputs 0..9 (all the second pool reads) use P1
+// rows / columns 0..11 only.  P1 row 12 and column 12 feed nothing and their gradient is exactly 0.
+constexpr int kP1Live = 12;
+constexpr int kConv1Tiles = kP1Live * kP1Live / 4;  // 36 conv1 row tiles of 4 pool windows
 // conv2 wgrad row tiles (first, count) per wave of the fused backward: waves w and w + 4 share a
-// SIMD; with tap skipping the dgrad MFMAs per SIMD are 192 / 168 / 144 / 144, so SIMDs 0..3 take
-// 4 / 4 / 5 / 5 of the 18 kernel-row tiles (292 / 268 / 269 / 269 MFMAs per SIMD).  The bias row
+// SIMD; with tap skipping the dgrad MFMAs per SIMD are 192 / 168 / 144 / 144, and SIMDs 0 and 1
+// also run 6 of the dgrad's pool-1 / conv1-wgrad epilogues (3 pixel tiles per wave) where SIMDs 2
+// and 3 run 4.  SIMDs 0..3 take 3 / 4 / 5 / 6 of the 18 kernel-row tiles: 267 / 268 / 269 / 294
+// MFMAs per SIMD.  (4 / 4 / 5 / 5 evens the MFMAs out, 292 / 268 / 269 / 269, but SIMD 0 then ended
+// the kernel 0.2-0.6 us after the others: profiles/mnist_dead_border.txt.)  The bias row
 // (db2 = the column sums of dC2 = the sums of the masked dP2 over the pool windows) is summed on
 // the VALU in the dP2 phase instead of a 19th MFMA tile against a unit vector.
-__constant__ int kFusedWgradTiles[8][2] = {{0, 2}, {2, 2}, {4, 3}, {7, 3}, {10, 2}, {12, 2}, {14, 2}, {16, 2}};
+__constant__ int kFusedWgradTiles[8][2] = {{0, 2}, {3, 2}, {7, 3}, {12, 3}, {2, 1}, {5, 2}, {10, 2}, {15, 3}};
 
 // phase stamp k < 4 of the fused backward, per wave, after the head stamps:
 // buf[grid*72 + (workgroup*8 + wave)*4 + k] (the buffer then holds grid * 104 words)
@@ -843,7 +850,8 @@ __device__ __forceinline__ void fused_conv_bwd(const MnistArgs& a, int bi, int c
   auto wgrad = [&]() {
     const int t0 = kFusedWgradTiles[wave][0], ntiles = kFusedWgradTiles[wave][1];
     if (ntiles == 2) fused_wgrad_tiles<2>(a, bi, cq, t0, P1s, dCs);
-    else fused_wgrad_tiles<3>(a, bi, cq, t0, P1s, dCs);
+    else if (ntiles == 3) fused_wgrad_tiles<3>(a, bi, cq, t0, P1s, dCs);
+    else fused_wgrad_tiles<1>(a, bi, cq, t0, P1s, dCs);
   };
   // the wgrad and the dgrad of a wave are independent: with kMnistVariantStagger the younger half
   // (waves 4-7, each the SIMD partner of wave w - 4) runs them in the opposite order, so the two
@@ -855,19 +863,21 @@ __device__ __forceinline__ void fused_conv_bwd(const MnistArgs& a, int bi, int c
   // ---- conv2 dgrad over this quarter's 16 output channels (a partial sum of dP1; everything after
   // it -- ReLU mask, pool-1 routing, conv1 wgrad -- is linear in dP1, so the four quarters'
   // conv1 weight gradients simply add up in the finalize reduction).  Waves 4nt .. 4nt+3 own input
-  // channels ci = 16nt + i and pixel tiles w, w + 4, w + 8 (16 pixels each), advanced together ----
+  // channels ci = 16nt + i and pixel tiles w, w + 4, w + 8 (16 pixels each), advanced together.
+  // Tile 10 (pixels 160..168, all in the dead row 12 of P1: no MFMA, an epilogue of exact zeros)
+  // and the empty tile 11 are not issued at all: waves 2, 3, 6, 7 run two tiles ----
   float dw[10];
 #pragma unroll
   for (int j = 0; j < 10; ++j) dw[j] = 0.f;
-  {
-    const int nt = wave >> 2, wt = wave & 3;
+  const int nt = wave >> 2, wt = wave & 3;
+  auto dgrad = [&](auto ktiles) {
+    constexpr int kT = decltype(ktiles)::value;
     const int ci = 16 * nt + i;
-    constexpr int kT = 3;
     f4 acc[kT][2];
     int ih[kT], iw[kT], khlo[kT], khhi[kT];
 #pragma unroll
     for (int u = 0; u < kT; ++u) {
-      const int t = wt + 4 * u;  // t = 11 (wave 3's third) is empty: khlo > khhi, no MFMA, no store
+      const int t = wt + 4 * u;  // <= 9
       const int Pc = min(t * 16 + i, 168);
       ih[u] = Pc / 13;
       iw[u] = Pc - ih[u] * 13;
@@ -935,7 +945,9 @@ __device__ __forceinline__ void fused_conv_bwd(const MnistArgs& a, int bi, int c
         }
       }
     }
-  }
+  };
+  if (wt < 2) dgrad(std::integral_constant<int, 3>{});  // (wave-uniform)
+  else dgrad(std::integral_constant<int, 2>{});
   if (swap) wgrad();
   bwd_stamp(a.stamps, 2);
 #pragma unroll
@@ -1062,9 +1074,19 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   auto ldw3 = [&](int j) { w3v[j] = ld4_buf(w3r, w3vo, j * 64 * 128 * 4); };
 #pragma unroll
   for (int j = 0; j < 6; ++j) ldw3(j);
-  // ---- conv1 on MFMA (K = 9 taps padded to 12): rows = 676 conv1 positions in pool-window-major
+  // ---- conv1 on MFMA (K = 9 taps padded to 12): rows = the conv1 positions in pool-window-major
   // order, so a 16-row tile holds 4 whole 2x2 windows and the maxpool happens in registers.
-  // 43 row tiles x 2 channel tiles; bias + relu after the max (they commute with it). ----
+  // Only the 12 x 12 pool windows that conv2 reads (kP1Live): the second pool takes floor(11 / 2) = 5
+  // windows, so conv2 outputs 0..9 and P1 rows / columns 0..11 are all that anything downstream
+  // uses.  Window w -> (w / 12, w % 12), stored at the 13-wide index: 36 row tiles x 2 channel
+  // tiles.  Waves 0-3 own 6 tiles (w + 4 s, s < 6), waves 4-7 -- the younger wave of each SIMD
+  // pair, which loses the issue arbitration -- 3 (24 + (w - 4) + 4 s, s < 3): both halves then end
+  // conv1 within 0.1 us of each other.  Bias + relu after the max (they commute with it).
+  // The 25 border cells (row 12, column 12) of P1s / a1s are ZEROED once per workgroup, by waves
+  // 4-7 behind their last tile: every consumer of the whole 13 x 13 grid (the fused backward's
+  // epilogue operands, store_saved_fwd and through it k_conv_bwd) then sees P1 = 0 there, i.e. a
+  // closed ReLU mask and argmax 0, and adds the same exact zeros as with the computed values (the
+  // gradient of a border cell is exactly 0 either way). ----
   {
     float bw[2][3];
 #pragma unroll
@@ -1085,15 +1107,21 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
     // reads of iteration it + 1 are issued right behind iteration it's MFMAs, so their LDS latency
     // hides behind the MFMA drain and the epilogue; the conv1 biases live in registers.
     const float bias[2] = {w1s[288 + i], w1s[288 + 16 + i]};
+    const int cwave = __builtin_amdgcn_readfirstlane(wave);
+    // tile slot s = 2 it + u holds tile mtb + 4 s; waves 4-7 issue nothing for s >= 3 (wave-uniform);
+    // they still run iterations 0 and 1 and so issue every W3 prefetch group
+    static_assert(kConv1Tiles == 4 * 6 + 4 * 3, "slot -> tile map of conv1");
+    auto live = [&](int it, int u) { return cwave < 4 || 2 * it + u < 3; };
+    const int mtb = wave < 4 ? wave : 20 + wave;
     float xa[2][2][3];
     auto load_x = [&](int buf, int it) {
-      const int mt0 = wave + 16 * it;
+      const int mt0 = mtb + 8 * it;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const int mt = min(mt0 + 8 * u, 42);
-        const int w = mt * 4 + (i >> 2), q = i & 3;
-        const int wc = min(w, 168);
-        const int y = 2 * (wc / 13) + (q >> 1), x = 2 * (wc % 13) + (q & 1);
+        if (!live(it, u)) continue;
+        const int w = (mt0 + 4 * u) * 4 + (i >> 2), q = i & 3;  // < 144
+        const int ph = w / kP1Live;
+        const int y = 2 * ph + (q >> 1), x = 2 * (w - ph * kP1Live) + (q & 1);
         const float* xb = xs + y * 28 + x;
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3) xa[buf][u][s3] = xb[tap_off[s3]];
@@ -1102,7 +1130,7 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
     load_x(0, 0);
 #pragma unroll
     for (int it = 0; it < 3; ++it) {
-      const int mt0 = wave + 16 * it;
+      const int mt0 = mtb + 8 * it;
       f4 acc[2][2];
 #pragma unroll
       for (int u = 0; u < 2; ++u)
@@ -1111,9 +1139,11 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
 #pragma unroll
       for (int s3 = 0; s3 < 3; ++s3)
 #pragma unroll
-        for (int u = 0; u < 2; ++u)
+        for (int u = 0; u < 2; ++u) {
+          if (!live(it, u)) continue;
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt) acc[u][nt] = mfma16x16x4(xa[it & 1][u][s3], bw[nt][s3], acc[u][nt]);
+        }
       __builtin_amdgcn_sched_barrier(0);
       if (it < 2) load_x((it + 1) & 1, it + 1);
       __builtin_amdgcn_sched_barrier(0);
@@ -1124,8 +1154,10 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        const int wo = (mt0 + 8 * u) * 4 + g;
-        if (mt0 + 8 * u >= 43 || wo >= 169) continue;
+        if (!live(it, u)) continue;
+        const int w = (mt0 + 4 * u) * 4 + g;
+        const int ph = w / kP1Live;
+        const int wo = ph * 13 + (w - ph * kP1Live);
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
           const f4 ac = acc[u][nt];
@@ -1139,6 +1171,16 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
           P1s[wo * kP1Stride + co] = v;
           a1s[wo * 32 + co] = (uint8_t)am;
         }
+      }
+    }
+    if (cwave >= 4) {
+      // the dead border: cells (12, 0..12) and (0..11, 12), 8 16-B chunks / 8 argmax words each
+      const int e = tid - 256;
+      if (e < 25 * 8) {
+        const int c = e >> 3, c4 = e & 7;
+        const int cell = c < 13 ? 12 * 13 + c : (c - 13) * 13 + 12;
+        st4(P1s + cell * kP1Stride + 4 * c4, zero4());
+        reinterpret_cast<unsigned*>(a1s)[cell * 8 + c4] = 0u;
       }
     }
   }
