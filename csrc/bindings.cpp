@@ -9,6 +9,7 @@
 #include <cmath>
 #include <vector>
 
+#include "kernels/accum.h"
 #include "kernels/mnist_cnn.h"
 #include "kernels/ops.h"
 #include "kernels/optim.h"
@@ -310,6 +311,26 @@ void clip_norm_chunk(at::Tensor g, at::Tensor partials, at::Tensor out, double c
 
 void clip_norm(at::Tensor g, at::Tensor partials, at::Tensor out, double clipnorm, OptDouble clipvalue) {
   clip_norm_chunk(g, partials, out, clipnorm, clipvalue, tdl::kClipChunk);
+}
+
+// One micro-step of gradient accumulation over whole slabs (csrc/kernels/accum.hip, one launch):
+// mode 0: A = G, mode 1: A = A + G, mode 2: G = (A + G) * c; zero_grad (modes 0, 1): G = 0 once it is read.
+// max_blocks lowers the grid cap (tests and scripts/bench_accum.py only).  Empty slabs launch nothing.
+void grad_accum(at::Tensor g, at::Tensor a, int64_t mode, double c, bool zero_grad, c10::optional<int64_t> max_blocks) {
+  check_slab_f32(g, "g");
+  check_slab_f32(a, "a");
+  TORCH_CHECK(g.numel() == a.numel(), "slab size mismatch: g has ", g.numel(), " elements, a has ", a.numel());
+  TORCH_CHECK(mode >= 0 && mode <= 2, "mode must be 0 (A = G), 1 (A += G) or 2 (G = (A + G) * c), got ", mode);
+  TORCH_CHECK(!(zero_grad && mode == 2), "zero_grad only with modes 0 and 1 (mode 2 writes its result to g)");
+  const int64_t n = g.numel();
+  const char* pg = reinterpret_cast<const char*>(g.data_ptr());
+  const char* pa = reinterpret_cast<const char*>(a.data_ptr());
+  TORCH_CHECK(n == 0 || pg + n * 4 <= pa || pa + n * 4 <= pg, "g and a must be different, non-overlapping slabs");
+  const int64_t mb = max_blocks.value_or(tdl::kAccumMaxBlocks);
+  TORCH_CHECK(mb >= 1 && mb <= tdl::kAccumMaxBlocks, "max_blocks must lie in [1, ", tdl::kAccumMaxBlocks, "]");
+  TORCH_CHECK(g.device() == a.device(), "g and a must be on the same device");
+  tdl::grad_accum_apply(g.data_ptr<float>(), a.data_ptr<float>(), n, (int)mode, (float)c, zero_grad, cur_stream(),
+                        (int)mb);
 }
 
 void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad, OptTensor gscale, OptDouble clipvalue) {
@@ -627,6 +648,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("clip_norm_chunk", &clip_norm_chunk, "clip_norm at another chunk size (measurement only)",
         pybind11::arg("g"), pybind11::arg("partials"), pybind11::arg("out"), pybind11::arg("clipnorm"),
         pybind11::arg("clipvalue"), pybind11::arg("chunk"));
+  m.attr("ACCUM_MAX_BLOCKS") = (int64_t)tdl::kAccumMaxBlocks;    // grid cap of k_grad_accum
+  m.attr("ACCUM_BLOCK_ELEMS") = (int64_t)tdl::kAccumBlockElems;  // elements a workgroup handles per grid pass
+  m.def("grad_accum", &grad_accum,
+        "gradient accumulation micro-step: mode 0 a = g, 1 a += g, 2 g = (a + g) * c (zero_grad: g := 0, modes 0/1)",
+        pybind11::arg("g"), pybind11::arg("a"), pybind11::arg("mode"), pybind11::arg("c"),
+        pybind11::arg("zero_grad") = false, pybind11::arg("max_blocks") = none);
   m.def("sgd", &sgd, "w -= lr * g over a flat slab (zero_grad: g := 0 afterwards)", pybind11::arg("w"),
         pybind11::arg("g"), pybind11::arg("lr"), pybind11::arg("zero_grad") = false,
         pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);

@@ -92,6 +92,8 @@ def eligible(model, dataset=None) -> Optional[str]:
         return f"optimizer {type(opt).__name__} has no fused update"
     if opt._clipped and not hasattr(ops.hip(), "clip_norm"):
         return "the extension has no clip_norm kernel (rebuild: python build_native.py)"
+    if opt._accumulating and not hasattr(ops.hip(), "grad_accum"):
+        return "the extension has no grad_accum kernel (rebuild: python build_native.py)"
     if opt.weight_decay and not isinstance(opt, optimizers.Adam):
         return "decoupled weight decay is fused for Adam/AdamW only"
     kern = {"Adam": "adam", "AdamW": "adam", "RMSprop": "rmsprop", "Adagrad": "adagrad", "LARS": "layer_tables",
@@ -219,9 +221,17 @@ class FusedMnistTrainer:
         with plain SGD: one all-reduce of the whole 900 KB slab with the SGD update fused into it
         (xGMI kernel), when the communicator has one.  Other optimizers: finalize leaves the
         gradient in G, their flat-slab kernel (csrc/kernels/optim.hip) applies it.  A clipped
-        optimizer is never plain: finalize(False) -> all-reduce -> clip_norm -> update kernel."""
+        optimizer is never plain: finalize(False) -> all-reduce -> clip_norm -> update kernel.  Neither is
+        an accumulating one (``gradient_accumulation_steps``): finalize(False) -> accumulate, and only the
+        cycle's last micro-step goes on to the all-reduce and the update; step k's phase is that of
+        ``iterations + k`` (``iterations`` advances once per execution), baked in at capture."""
         opt = self.optimizer
         self._step_k = k
+        if opt._accumulating:
+            st.finalize(False)
+            if opt.accumulate(self.G, k):
+                self._reduce_and_update()
+            return
         plain = self._plain_sgd
         if self.R == 1 and plain:
             st.finalize(True, keep_grad=False)  # (nothing reads G on this path)
@@ -385,9 +395,10 @@ class FusedMnistTrainer:
     @property
     def _plain_sgd(self) -> bool:
         # (gradient clipping needs the whole reduced gradient before any update: never the SGD inside
-        # finalize, all_reduce_sgd, the exchange-in-finalize channel or the two-bucket overlap)
+        # finalize, all_reduce_sgd, the exchange-in-finalize channel or the two-bucket overlap; gradient
+        # accumulation folds the local gradient first and updates on the cycle's last micro-step only)
         opt = self.optimizer
-        return type(opt).__name__ == "SGD" and opt.momentum == 0 and not opt._clipped
+        return type(opt).__name__ == "SGD" and opt.momentum == 0 and not opt._clipped and not opt._accumulating
 
     def _update(self, lo: int = 0, hi: Optional[int] = None):
         from .. import ops
@@ -416,9 +427,13 @@ class FusedMnistTrainer:
         if b == 0:
             # this replica got no samples of a tiny final batch: contribute zero gradients
             self.G.zero_()
+            opt = self.optimizer
+            if not opt.accumulate(self.G):  # (every rank is in the same phase: none communicates)
+                opt.iterations += 1
+                return
             if self.R > 1:
                 self.comm.all_reduce(self.G, "sum")
-            self.optimizer.apply_flat(self.W, self.G)
+            opt.apply_flat(self.W, self.G, accumulated=True)
             return
         # one persistent index buffer per ragged size (the step object is cached by its address),
         # filled through a pinned staging buffer without a host sync
@@ -440,10 +455,18 @@ class FusedMnistTrainer:
         self._train_step(st, 0, global_b)
         self.optimizer.iterations += 1
 
-    def _graph_for(self, K: int, b: int, slot: int = 0):
+    def _graph_key(self, K: int, b: int, slot: int, t_add: int = 0) -> tuple:
+        """Key of the K-step execution graph of an index slot that starts ``t_add`` micro-steps from now; with
+        gradient accumulation it carries the execution's starting phase (every step's mode is baked in)."""
+        opt = self.optimizer
+        return (K, b, slot, opt._accum_phase(t_add)) if opt._accumulating else (K, b, slot)
+
+    def _graph_for(self, K: int, b: int, slot: int = 0, t_add: int = 0):
         """Graph of one K-step execution reading its sample ids from its own index buffer; the
-        slots rotate so the host uploads execution i+1's indices while execution i runs."""
-        g = self._graphs.get((K, b, slot))
+        slots rotate so the host uploads execution i+1's indices while execution i runs.  ``t_add``: the
+        execution starts that many micro-steps from now (warm_graphs captures ahead)."""
+        key = self._graph_key(K, b, slot, t_add)
+        g = self._graphs.get(key)
         if g is not None:
             return g
         idx_buf = torch.zeros(K * b, dtype=torch.int32, device=self.device)
@@ -459,9 +482,14 @@ class FusedMnistTrainer:
             if self.capture_comm:
                 # whole execution (K steps incl. all-reduce + optimizer) in one graph
                 graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, stream=s):
-                    for k in range(K):
-                        self._train_step(st, k * b, b * self.R)
+                it0 = self.optimizer.iterations
+                self.optimizer.iterations = it0 + t_add  # (the accumulation phase of step k: iterations + k)
+                try:
+                    with torch.cuda.graph(graph, stream=s):
+                        for k in range(K):
+                            self._train_step(st, k * b, b * self.R)
+                finally:
+                    self.optimizer.iterations = it0
             else:
                 # one graph per step holding the fused fwd/bwd/finalize; the RCCL all-reduce and
                 # the SGD kernel are issued eagerly between replays
@@ -479,7 +507,7 @@ class FusedMnistTrainer:
             for k, v in saved[2].items():
                 self.optimizer.slots()[k].copy_(v)
         g = (graph, idx_buf, st)
-        self._graphs[(K, b, slot)] = g
+        self._graphs[key] = g
         return g
 
     def warm_graphs(self, steps: int, b: Optional[int] = None):
@@ -491,9 +519,14 @@ class FusedMnistTrainer:
         sizes = {self.K} if steps >= self.K else set()
         if steps % self.K:
             sizes.add(steps % self.K)
-        for K in sizes:
+        # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
+        a = self.optimizer.gradient_accumulation_steps if self.optimizer._accumulating else 1
+        starts = [(self.K, i * self.K) for i in range(min(steps // self.K, a))]
+        if steps % self.K:
+            starts.append((steps % self.K, steps - steps % self.K))
+        for K, t_add in starts:
             for slot in range(self._nslots):
-                self._graph_for(K, b, slot)
+                self._graph_for(K, b, slot, t_add)
         # pinned staging buffers of every slot at full size now: a pinned (hipHostMalloc)
         # allocation inside the launch loop waited ~30 ms for the device
         if sizes:
@@ -592,7 +625,8 @@ class FusedMnistTrainer:
                 for k, gk in enumerate(graph):
                     gk.replay()
                     self._step_k = k
-                    self._reduce_and_update()
+                    if opt.accumulate(self.G, k):  # (True when accumulation is off)
+                        self._reduce_and_update()
             elif graph is not None:
                 graph.replay()
             else:

@@ -45,6 +45,10 @@ def make_group_trainer(model):
     models, group = _models_and_group(model)
     if all(d.type == "cuda" for d in group.devices) and os.environ.get("TDL_MIRRORED_DEVICE_PATH", "1") == "1":
         reason = F.eligible(model)
+        if reason is None and getattr(model.optimizer, "_accumulating", False):
+            # (the per-device captured path has no accumulating micro-step yet; the threaded trainer runs the
+            # generic train_step, which has)
+            reason = "gradient accumulation: fused engine in process mode only"
         if reason is None:
             return MirroredFusedTrainer(model, models, group)
         model._fused_reason = reason

@@ -231,7 +231,8 @@ class GenericTrainer:
         layer order) are launched asynchronously as soon as every gradient inside is final.  The
         bucket size comes from compile(bucket_bytes=...), else CommunicationOptions.bytes_per_pack,
         else the size/topology plan of parallel/bucketing.py; CommunicationOptions.all_reduce_dtype
-        sets the dtype on the wire."""
+        sets the dtype on the wire.  While an optimizer built with ``gradient_accumulation_steps`` is compiled
+        the buckets are not armed: they would reduce a gradient that is not final (train_step)."""
         from ..parallel import bucketing
 
         opts = getattr(self.strategy.extended, "communication_options", None)
@@ -245,7 +246,9 @@ class GenericTrainer:
         self._wire_full = None
         if self.comm.world_size == 1:
             return None
-        if explicit == 0:
+        if explicit == 0 or getattr(self.model.optimizer, "_accumulating", False):
+            # (gradient accumulation: a bucket's hook would reduce a micro-step's gradient, which is not final
+            # before the fold of the cycle's last micro-step; that micro-step all-reduces the whole slab once)
             self.plan.n_buckets, self.plan.bucket_bytes = 1, self.plan.wire_bytes
             return None
         xg = getattr(self.comm, "xgmi", None)
@@ -484,6 +487,29 @@ class GenericTrainer:
         for b in (self.model.__dict__.get("_grad_boxes") or {}).values():
             if b.g is not None:  # a parked gradient contribution nobody collected
                 raise RuntimeError("fused gradient sum lost a contribution (keras/fusion.py grad boxes)")
+        opt = self.optimizer
+        apply = True
+        if opt._accumulating:
+            # gradient accumulation: the LOCAL gradient is folded into the optimizer's accumulator slab; only
+            # the cycle's last micro-step goes on to the all-reduce (one, of the whole slab) and the update
+            with torch.no_grad(), trace_range("tdl.accumulate"):
+                opt._zero_grad_after, opt._zeroed_grad = G.is_cuda, False
+                try:
+                    apply = opt.accumulate(G)
+                finally:
+                    opt._zero_grad_after = False
+        if not apply:
+            with torch.no_grad():
+                opt.iterations += 1
+                # (the accumulate kernel zeroed G after reading it)
+                self._g_clean = G.data_ptr() if opt._zeroed_grad else None
+                opt._zeroed_grad = False
+                if per_ex is not None:
+                    self.loss_tracker.update_state(per_ex.detach())
+                    yp = y_pred.detach()
+                    for m in self.metrics:
+                        m.update_state(y, yp, sw)
+            return
         if self.comm.world_size > 1 and not self._skip_comm:
             with trace_range("tdl.allreduce"):
                 if self._buckets is not None:
@@ -505,12 +531,17 @@ class GenericTrainer:
                 else:
                     self.comm.all_reduce(G, "sum")
         with torch.no_grad(), trace_range("tdl.optimizer"):
-            opt = self.optimizer
             opt._zero_grad_after, opt._zeroed_grad = G.is_cuda, False
             try:
-                opt.apply_flat(self.W, G, sync_lr=sync_lr, t_add=t_add)
+                opt.apply_flat(self.W, G, sync_lr=sync_lr, t_add=t_add, accumulated=True)
             finally:
                 opt._zero_grad_after = False
+            if opt._accumulating and G.is_cuda and not opt._zeroed_grad:
+                # the other micro-steps of a cycle leave G clean (the accumulate kernel zeroes it), so this one
+                # does too -- the fill the next step would start with -- and a captured step's choice between
+                # "G is clean" and "zero G first" never depends on which micro-step ran before the capture
+                G.zero_()
+                opt._zeroed_grad = True
             # (only an optimizer kernel that zeroed G after reading it marks this slab clean)
             self._g_clean = G.data_ptr() if opt._zeroed_grad else None
             opt._zeroed_grad = False
@@ -557,6 +588,8 @@ class GenericTrainer:
         if not self._graphable():
             return False
         key = (global_n,) + tuple((tuple(t.shape), t.dtype) for t in flat)
+        if self.optimizer._accumulating:  # the accumulate mode is baked into the capture
+            key += (("accum", self._accum_mode()),)
         ent = self._graphs.get(key)
         if ent is None:
             seen = self._seen.get(key, 0) + 1
@@ -580,6 +613,18 @@ class GenericTrainer:
         graph.replay()
         self.optimizer.iterations += 1
         return True
+
+    def _accum_mode(self) -> str:
+        """The kind of the next micro-step of an accumulating optimizer: first / middle / last of its cycle."""
+        opt = self.optimizer
+        p = opt._accum_phase()
+        return "last" if p == opt.gradient_accumulation_steps - 1 else ("first" if p == 0 else "middle")
+
+    def _exec_key(self, K: int, b: int, t_add: int = 0) -> tuple:
+        """Key of the K-step execution graph at batch size b that starts ``t_add`` micro-steps from now; with
+        gradient accumulation it carries the execution's starting phase (every step's mode is baked in)."""
+        opt = self.optimizer
+        return ("dev", K, b, opt._accum_phase(t_add)) if opt._accumulating else ("dev", K, b)
 
     def _capture(self, batch, global_n: int):
         flat = D.flatten(batch)
@@ -679,9 +724,14 @@ class GenericTrainer:
         sizes = ({K} if steps >= K else set()) | ({steps % K} if steps % K else set())
         if getattr(self, "_dev_idx", None) is None or self._dev_idx.numel() < max(sizes) * b:
             self._dev_upload(np.zeros(max(sizes) * b, dtype=np.int32))
-        for k in sizes:
-            if ("dev", k, b) not in self._graphs:
-                self._dev_capture(k, b)
+        # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
+        a = self.optimizer.gradient_accumulation_steps if self.optimizer._accumulating else 1
+        starts = [(K, i * K) for i in range(min(steps // K, a))]
+        if steps % K:
+            starts.append((steps % K, steps - steps % K))
+        for k, t_add in starts:
+            if self._exec_key(k, b, t_add) not in self._graphs:
+                self._dev_capture(k, b, t_add)
 
     def _run_device(self, handler, steps: int) -> int:
         import gc
@@ -709,7 +759,7 @@ class GenericTrainer:
             K = idx.size // b
             self._dev_upload(idx)
             opt._sync_lr()
-            graph = self._graphs.get(("dev", K, b))
+            graph = self._graphs.get(self._exec_key(K, b))
             if (graph is None and b in self._dev_warm and self._graph_ok is not False and
                     os.environ.get("TDL_GENERIC_DEVICE_EAGER", "0") != "1"):
                 graph = self._dev_capture(K, b)
@@ -727,13 +777,17 @@ class GenericTrainer:
             done += K
         return done
 
-    def _dev_capture(self, K: int, b: int):
+    def _dev_capture(self, K: int, b: int, t_add: int = 0):
+        """Capture the K-step execution that starts ``t_add`` micro-steps from now (only its accumulation
+        phase depends on the start: the step count the kernels read is on the device)."""
         dev = self.device
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         s = torch.cuda.Stream(dev)
         s.wait_stream(torch.cuda.current_stream(dev))
         it0 = self.optimizer.iterations
+        key = self._exec_key(K, b, t_add)
+        self.optimizer.iterations = it0 + t_add
         try:
             with torch.cuda.graph(graph, stream=s):
                 for k in range(K):
@@ -748,7 +802,7 @@ class GenericTrainer:
         finally:
             self.optimizer.iterations = it0  # capture records, it does not run a step
         torch.cuda.current_stream(dev).wait_stream(s)
-        self._graphs[("dev", K, b)] = graph
+        self._graphs[key] = graph
         return graph
 
     @torch.no_grad()

@@ -24,6 +24,13 @@ and ratios from them in a fixed order (bit-identical on every run and replica), 
 chunk tables are built and validated once on the host (``_C.layer_tables``).  ``last_layer_ratios``
 / ``last_layer_norms`` expose the last step's words.  The per-variable torch formulas are the CPU
 implementation.  ``clipnorm`` stays one norm over the whole slab for every optimizer.
+
+Gradient accumulation (``gradient_accumulation_steps=k`` on every optimizer): the local gradients of k
+micro-steps are folded in f32 into one more slab, the slot ``"gradient_accumulator"`` (``accumulate``: one
+launch of ``_C.grad_accum``, csrc/kernels/accum.hip, on the GPU), and only the k-th micro-step all-reduces,
+clips and updates, on the cycle's mean gradient.  ``iterations`` counts micro-steps (Keras 3's counting) and
+the phase of a micro-step is ``iterations mod k``, known to the host at launch and at capture time: no device
+counter.  Keras is not installed where this was written: parity with its implementation is unpinned.
 """
 from __future__ import annotations
 
@@ -37,8 +44,12 @@ from . import schedules as _sched
 
 class Optimizer:
     def __init__(self, learning_rate=0.001, name="Optimizer", clipnorm=None, clipvalue=None, global_clipnorm=None,
-                 weight_decay=None, **kwargs):
+                 weight_decay=None, gradient_accumulation_steps=None, **kwargs):
         self.name = name
+        k = gradient_accumulation_steps
+        if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+            raise ValueError(f"gradient_accumulation_steps must be None or an integer >= 1, got {k!r}")
+        self.gradient_accumulation_steps = k
         self._lr = learning_rate
         self.clipnorm, self.clipvalue, self.global_clipnorm = clipnorm, clipvalue, global_clipnorm
         self.weight_decay = weight_decay
@@ -125,7 +136,7 @@ class Optimizer:
 
             self._clip_out = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
             self._clip_partials = torch.zeros(max(1, ops.hip().clip_partials(n)), dtype=torch.float64, device=device)
-        for k in self._slot_names():
+        for k in self._slot_names() + ([ACCUMULATOR] if self._accumulating else []):
             old = self._slots.get(k)
             self._slots[k] = old.to(device) if (old is not None and old.numel() == n) else torch.zeros(
                 n, dtype=torch.float32, device=device)
@@ -176,11 +187,67 @@ class Optimizer:
             n = torch.linalg.vector_norm(G)
             G.mul_(torch.clamp(norm / (n + 1e-12), max=1.0))
 
-    def apply_flat(self, W: torch.Tensor, G: torch.Tensor, sync_lr: bool = True, t_add: int = 0):
+    # ------------------------------------------------------------------ gradient accumulation
+    @property
+    def _accumulating(self) -> bool:
+        return (self.gradient_accumulation_steps or 1) > 1
+
+    def _accum_phase(self, t_add: int = 0) -> int:
+        """The phase of the micro-step ``t_add`` steps from now: ``iterations mod k`` before its increment.  The
+        host knows it at launch and at capture time (no device counter)."""
+        return (int(self.iterations) + int(t_add)) % self.gradient_accumulation_steps
+
+    def accumulate(self, G: torch.Tensor, t_add: int = 0) -> bool:
+        """The fold of one micro-step over the gradient slab ``G`` into the slot ``"gradient_accumulator"``
+        (``A``), by the phase p of the micro-step (``t_add``: its offset inside an execution whose first step is
+        ``iterations``), every operation one f32 rounding:
+
+            p == 0: A = G        0 < p < k-1: A = A + G        p == k-1: G = (A + G) * float32(1 / k)
+
+        Returns whether this is the apply micro-step (p == k-1): ``G`` then holds the mean gradient of the cycle
+        and the caller all-reduces, clips and updates as an unaccumulated step would.  On a GPU slab it is one
+        ``_C.grad_accum`` launch (csrc/kernels/accum.hip; capturable, the mode is baked in at capture), which
+        also zeroes ``G`` on the other micro-steps when the trainer asked for it (``_zero_grad_after``); the
+        torch formulas are the CPU implementation.  A no-op returning True when accumulation is off."""
+        if not self._accumulating:
+            return True
+        if self._n != G.numel() or self._device != G.device:
+            self.build(G.numel(), G.device)
+        k = self.gradient_accumulation_steps
+        p = self._accum_phase(t_add)
+        A = self._slots[ACCUMULATOR]
+        mode = 0 if p == 0 else (2 if p == k - 1 else 1)
+        c = _f32(1.0 / k)
+        if G.device.type == "cuda":
+            from .. import ops
+
+            if G.dtype != torch.float32 or not hasattr(ops.hip(), "grad_accum"):
+                raise RuntimeError("gradient accumulation: the extension has no grad_accum kernel for the GPU slab "
+                                   "(rebuild: python build_native.py)")
+            zero = mode != 2 and bool(getattr(self, "_zero_grad_after", False))
+            ops.hip().grad_accum(G, A, mode, c, zero_grad=zero)
+            if zero:
+                self._zeroed_grad = True
+        elif mode == 0:
+            A.copy_(G)
+        elif mode == 1:
+            A.add_(G)
+        else:
+            torch.add(A, G, out=G)
+            G.mul_(c)
+        return mode == 2
+
+    def apply_flat(self, W: torch.Tensor, G: torch.Tensor, sync_lr: bool = True, t_add: int = 0,
+                   accumulated: bool = False):
         """w <- update(w, g) over the whole slab (gradients already all-reduced).  ``t_add``: this
-        step's offset from ``t_dev`` inside a multi-step execution (only Adam reads a step count)."""
+        step's offset from ``t_dev`` inside a multi-step execution (only Adam reads a step count).
+        With gradient accumulation on, ``G`` is first folded (``accumulate``) unless the caller has done so
+        (``accumulated=True``); a micro-step that is not the cycle's last only counts."""
         if self._n != W.numel() or self._device != W.device:
             self.build(W.numel(), W.device)
+        if self._accumulating and not accumulated and not self.accumulate(G):
+            self.iterations += 1
+            return
         if sync_lr:
             self._sync_lr()
         if self.device_update(W, G, t_add):  # clip + (decay +) update in the kernel
@@ -256,7 +323,8 @@ class Optimizer:
         if isinstance(lr, _sched.LearningRateSchedule):
             lr = _sched.serialize(lr)
         return {"name": self.name, "learning_rate": lr, "clipnorm": self.clipnorm, "clipvalue": self.clipvalue,
-                "global_clipnorm": self.global_clipnorm}
+                "global_clipnorm": self.global_clipnorm,
+                "gradient_accumulation_steps": self.gradient_accumulation_steps}
 
     @classmethod
     def from_config(cls, cfg):
@@ -272,6 +340,9 @@ class Optimizer:
         self.iterations = int(st.get("iterations", 0))
         for k, v in st.get("slots", {}).items():
             self._slots[k] = v.to(self._device) if self._device is not None else v.clone()
+
+
+ACCUMULATOR = "gradient_accumulator"  # the slot of the f32 accumulator slab
 
 
 def _kernel_present(kernel: str) -> bool:
