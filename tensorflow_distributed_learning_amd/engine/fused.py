@@ -23,8 +23,6 @@ from __future__ import annotations
 
 import gc
 import os
-import queue
-import threading
 import time
 from typing import Dict, Optional
 
@@ -34,6 +32,7 @@ import torch
 from ..data import device as DD
 from ..models import mnist_cnn as M
 from ..parallel import input_lib
+from . import execution as EX
 
 
 def _is_reference_cnn(model) -> bool:
@@ -123,7 +122,23 @@ def _same_source(a, b) -> bool:
     return a is not None and b is not None and a[0] is b[0] and a[1] is b[1] and a[2:] == b[2:]
 
 
-class FusedMnistTrainer:
+def _reference_columns(lp, labels: bool = True):
+    """(x, y) of a lowered pipeline when they are the reference model's input (y is None without
+    ``labels``); None otherwise, or when the pipeline did not lower (``lp`` is None)."""
+    if lp is None:
+        return None
+    cols = lp.columns if isinstance(lp.columns, (tuple, list)) else (lp.columns,)
+    x = cols[0]
+    y = cols[1] if labels and len(cols) > 1 else None
+    if not isinstance(x, torch.Tensor) or tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28)) or \
+            x.dtype != torch.float32:
+        return None
+    if labels and (not isinstance(y, torch.Tensor) or y.dim() != 1):
+        return None
+    return x, y
+
+
+class FusedMnistTrainer(EX.Prefetching):
     kind = "fused"
 
     def __init__(self, model):
@@ -164,11 +179,14 @@ class FusedMnistTrainer:
         # index-upload slots (one captured graph each): the host may run this many executions ahead
         # of the GPU, which absorbs host hiccups such as an epoch's shuffle (~ms) without starving it
         self._nslots = max(2, int(os.environ.get("TDL_INDEX_SLOTS", "4")))
-        self._ragged_bufs, self._ragged_stage, self._ragged_ev = {}, None, None
+        self._ring = EX.IndexRing(self.device, self._nslots)
+        self._ragged_bufs = {}
         # diagnostics: host seconds per execution (index take, upload, graph launch)
         self._host_times = [] if os.environ.get("TDL_HOST_TIMING") == "1" else None
-        # one execution's indices taken and uploaded ahead of its launch (prefetch())
-        self._ready = None
+        self._last_take = (0.0, 0.0, 0.0)
+        self._comm_prepared, self._xchg = False, None  # (_prepare_comm)
+        self._eval_cache = None
+        self._handlers_b = None
 
     @property
     def capture_comm(self) -> bool:
@@ -186,14 +204,12 @@ class FusedMnistTrainer:
     # ------------------------------------------------------------------ data
     def prepare(self, dataset):
         lp = DD.lower(dataset)
-        if lp is None:
-            return None
-        x, y = (lp.columns if isinstance(lp.columns, (tuple, list)) else (None, None))[:2]
-        if x is None or y is None or tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28)) or \
-                x.dtype != torch.float32 or y.dim() != 1:
+        cols = _reference_columns(lp)
+        if cols is None:
             return None
         if lp.batch_size % self.R:
             raise ValueError(f"global batch {lp.batch_size} is not divisible by {self.R} replicas")
+        x, y = cols
         key = _source_key(x, y)
         if not _same_source(self._data_key, key):
             self.X = x.reshape(len(x), 28, 28, 1).to(self.device, torch.float32).contiguous()
@@ -202,7 +218,7 @@ class FusedMnistTrainer:
             self._steps, self._graphs = {}, {}
         policy = input_lib.effective_policy(dataset) if self.R > 1 else None
         seed = input_lib.shared_seed(self.strategy) if policy is not None and policy.name in ("DATA", "FILE") else None
-        h = DeviceHandler(lp, seed, self.rank, self.R)
+        h = EX.DeviceHandler(lp, seed, self.rank, self.R)
         self._handlers_b = [h.b]
         return h
 
@@ -226,11 +242,10 @@ class FusedMnistTrainer:
         cycle's last micro-step goes on to the all-reduce and the update; step k's phase is that of
         ``iterations + k`` (``iterations`` advances once per execution), baked in at capture."""
         opt = self.optimizer
-        self._step_k = k
         if opt._accumulating:
             st.finalize(False)
             if opt.accumulate(self.G, k):
-                self._reduce_and_update()
+                self._reduce_and_update(k)
             return
         plain = self._plain_sgd
         if self.R == 1 and plain:
@@ -243,7 +258,7 @@ class FusedMnistTrainer:
         st.finalize(False)
         if self.R > 1 and plain and self.comm.all_reduce_sgd(self.G, self.W, opt.lr_dev):
             return
-        self._reduce_and_update()
+        self._reduce_and_update(k)
 
     def _train_step(self, st, off: int, global_b: int):
         """One whole step on the current stream.  R > 1 default (serial): forward + backward,
@@ -254,9 +269,10 @@ class FusedMnistTrainer:
         follows finalize().  With the xGMI one-shot communicator each bucket's all-reduce also
         applies plain SGD to its own parameter range (W[dense_offset:] is not read again in the
         step), so no separate optimizer kernel runs; otherwise the optimizer waits for both."""
+        k = off // max(1, st.b)
         if self.R == 1 or not self.overlap or not self._plain_sgd:
             st.forward_backward(off)
-            self._apply(st, global_b, off // max(1, st.b))
+            self._apply(st, global_b, k)
             return
         main = torch.cuda.current_stream(self.device)
         if self._comm_stream is None:
@@ -264,12 +280,11 @@ class FusedMnistTrainer:
         cs = self._comm_stream
         d0 = st.dense_offset
         G, W = self.G, self.W
-        fuse = self.optimizer.momentum == 0
         lr = self.optimizer.lr_dev
         st.forward_dense(off)
         cs.wait_stream(main)
         with torch.cuda.stream(cs):
-            dense_fused = fuse and self.comm.all_reduce_sgd(G[d0:], W[d0:], lr)
+            dense_fused = self.comm.all_reduce_sgd(G[d0:], W[d0:], lr)
             if not dense_fused:
                 self.comm.all_reduce(G[d0:], "sum")
         st.backward_conv()
@@ -281,10 +296,7 @@ class FusedMnistTrainer:
         with torch.cuda.stream(cs):
             self.comm.all_reduce(G[:d0], "sum")
         main.wait_stream(cs)
-        if dense_fused:
-            self._update(0, d0)
-        else:
-            self._update()
+        self._update(0, d0 if dense_fused else None, k)
 
     def _prepare_comm(self, st):
         """Collective set-up of the communicator's all-reduce channels for this step's buckets
@@ -293,7 +305,7 @@ class FusedMnistTrainer:
         (one exchange slot per finalize workgroup)."""
         if self.R == 1:
             return
-        if not getattr(self, "_comm_prepared", False):
+        if not self._comm_prepared:
             n, d0 = self.W.numel(), st.dense_offset
             self.comm.prepare_all_reduce(n - d0, d0, n)
             self._xchg = None
@@ -400,28 +412,19 @@ class FusedMnistTrainer:
         opt = self.optimizer
         return type(opt).__name__ == "SGD" and opt.momentum == 0 and not opt._clipped and not opt._accumulating
 
-    def _update(self, lo: int = 0, hi: Optional[int] = None):
-        from .. import ops
-
+    def _update(self, lo: int = 0, hi: Optional[int] = None, k: int = 0):
+        """The optimizer's own flat-slab kernel over [lo, hi) for step ``k`` of its execution (Adam's step
+        offset, baked into the captured graph).  The whole slab, except for the two buckets of the overlap
+        path, which is plain SGD only (see _plain_sgd: no clip, no momentum slot to slice)."""
         opt = self.optimizer
-        C = ops.hip()
         W, G = self.W[lo:hi], self.G[lo:hi]
-        if type(opt).__name__ != "SGD":
-            # whole slab only (lo, hi cover it: the two-bucket split is SGD-only); Adam's step offset
-            # inside the execution is baked into the captured graph
-            if not opt.device_update(W, G, getattr(self, "_step_k", 0)):
-                raise RuntimeError(f"fused trainer: {type(opt).__name__} has no device update on {W.device}")
-            return
-        clip = opt.device_clip(G)  # (a clipped optimizer updates the whole slab: see _plain_sgd)
-        if opt.momentum == 0:
-            C.sgd(W, G, opt.lr_dev, **clip)
-        else:
-            C.sgd_momentum(W, G, opt._slots["momentum"][lo:hi], opt.lr_dev, opt.momentum, opt.nesterov, **clip)
+        if not opt.device_update(W, G, k):
+            raise RuntimeError(f"fused trainer: {type(opt).__name__} has no device update on {W.device}")
 
-    def _reduce_and_update(self):
+    def _reduce_and_update(self, k: int):
         if self.R > 1:
             self.comm.all_reduce(self.G, "sum")
-        self._update()
+        self._update(k=k)
 
     def _run_eager(self, idx_np: np.ndarray, b: int, global_b: int):
         if b == 0:
@@ -436,36 +439,24 @@ class FusedMnistTrainer:
             opt.apply_flat(self.W, self.G, accumulated=True)
             return
         # one persistent index buffer per ragged size (the step object is cached by its address),
-        # filled through a pinned staging buffer without a host sync
+        # filled through the next slot of the staging ring without a host sync
         key = ("ragged", b)
         idx_buf = self._ragged_bufs.get(key)
         if idx_buf is None:
             idx_buf = torch.zeros(b, dtype=torch.int32, device=self.device)
             self._ragged_bufs[key] = idx_buf
-        if self._ragged_ev is not None:
-            self._ragged_ev.synchronize()
-        if self._ragged_stage is None or self._ragged_stage.numel() < b:
-            self._ragged_stage = torch.empty(max(b, 256), dtype=torch.int32, pin_memory=True)
-        self._ragged_stage[:b].numpy()[:] = idx_np
-        idx_buf.copy_(self._ragged_stage[:b], non_blocking=True)
-        self._ragged_ev = torch.cuda.Event()
-        self._ragged_ev.record(torch.cuda.current_stream(self.device))
+        self._ring.upload(idx_np, idx_buf, self._ring.next_slot())
         st = self._step(b, idx_buf, global_b)
         self._prepare_comm(st)
         self._train_step(st, 0, global_b)
         self.optimizer.iterations += 1
 
-    def _graph_key(self, K: int, b: int, slot: int, t_add: int = 0) -> tuple:
-        """Key of the K-step execution graph of an index slot that starts ``t_add`` micro-steps from now; with
-        gradient accumulation it carries the execution's starting phase (every step's mode is baked in)."""
-        opt = self.optimizer
-        return (K, b, slot, opt._accum_phase(t_add)) if opt._accumulating else (K, b, slot)
-
     def _graph_for(self, K: int, b: int, slot: int = 0, t_add: int = 0):
         """Graph of one K-step execution reading its sample ids from its own index buffer; the
         slots rotate so the host uploads execution i+1's indices while execution i runs.  ``t_add``: the
         execution starts that many micro-steps from now (warm_graphs captures ahead)."""
-        key = self._graph_key(K, b, slot, t_add)
+        opt = self.optimizer
+        key = EX.accum_key(opt, (K, b, slot), t_add)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -474,29 +465,18 @@ class FusedMnistTrainer:
         self._prepare_comm(st)
         graph = None
         if self.capture:
-            s = torch.cuda.Stream(self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            torch.cuda.synchronize(self.device)
-            saved = (self.W.clone(), self.metrics_dev.clone(),
-                     {k: v.clone() for k, v in self.optimizer.slots().items()})
+            saved = (self.W.clone(), self.metrics_dev.clone(), {k: v.clone() for k, v in opt.slots().items()})
             if self.capture_comm:
                 # whole execution (K steps incl. all-reduce + optimizer) in one graph
-                graph = torch.cuda.CUDAGraph()
-                it0 = self.optimizer.iterations
-                self.optimizer.iterations = it0 + t_add  # (the accumulation phase of step k: iterations + k)
-                try:
-                    with torch.cuda.graph(graph, stream=s):
-                        for k in range(K):
-                            self._train_step(st, k * b, b * self.R)
-                finally:
-                    self.optimizer.iterations = it0
+                with EX.capturing(self.device, opt, t_add) as graph:
+                    for k in range(K):
+                        self._train_step(st, k * b, b * self.R)
             else:
                 # one graph per step holding the fused fwd/bwd/finalize; the RCCL all-reduce and
                 # the SGD kernel are issued eagerly between replays
                 graph = []
                 for k in range(K):
-                    gk = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(gk, stream=s):
+                    with EX.capturing(self.device, opt) as gk:
                         st.forward_backward(k * b)
                         st.finalize(False)
                     graph.append(gk)
@@ -512,51 +492,19 @@ class FusedMnistTrainer:
 
     def warm_graphs(self, steps: int, b: Optional[int] = None):
         """Capture every graph ``run_train(steps)`` will replay, ahead of a timed region."""
-        if b is None and getattr(self, "_handlers_b", None):
+        if b is None and self._handlers_b:
             b = self._handlers_b[0]
         if b is None:
             return
-        sizes = {self.K} if steps >= self.K else set()
-        if steps % self.K:
-            sizes.add(steps % self.K)
         # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
-        a = self.optimizer.gradient_accumulation_steps if self.optimizer._accumulating else 1
-        starts = [(self.K, i * self.K) for i in range(min(steps // self.K, a))]
-        if steps % self.K:
-            starts.append((steps % self.K, steps - steps % self.K))
+        starts = EX.execution_starts(steps, self.K, self.optimizer.gradient_accumulation_steps or 1)
         for K, t_add in starts:
             for slot in range(self._nslots):
                 self._graph_for(K, b, slot, t_add)
-        # pinned staging buffers of every slot at full size now: a pinned (hipHostMalloc)
-        # allocation inside the launch loop waited ~30 ms for the device
-        if sizes:
-            self._ensure_stage(max(sizes) * b)
+        if starts:
+            self._ring.reserve(max(K for K, _ in starts) * b)
 
-    def _ensure_stage(self, n: int):
-        if not hasattr(self, "_stage"):
-            self._stage, self._stage_ev, self._slot = [None] * self._nslots, [None] * self._nslots, 0
-        for slot in range(self._nslots):
-            if self._stage[slot] is None or self._stage[slot].numel() < n:
-                if self._stage_ev[slot] is not None:
-                    self._stage_ev[slot].synchronize()
-                self._stage[slot] = torch.empty(max(n, 1024), dtype=torch.int32, pin_memory=True)
-
-    def _upload(self, idx: np.ndarray, idx_buf: torch.Tensor, slot: int):
-        """Asynchronous H2D copy of an execution's indices through a pinned staging buffer."""
-        n = idx.size
-        stage = self._stage[slot]
-        if stage is None or stage.numel() < n:
-            stage = torch.empty(max(n, 1024), dtype=torch.int32, pin_memory=True)
-            self._stage[slot] = stage
-        elif self._stage_ev[slot] is not None:
-            self._stage_ev[slot].synchronize()  # the previous copy out of this buffer has run
-        stage[:n].numpy()[:] = idx
-        idx_buf[:n].copy_(stage[:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self._stage_ev[slot] = ev
-
-    def _take_upload(self, handler: "DeviceHandler", K: int):
+    def _take_upload(self, handler: EX.DeviceHandler, K: int):
         """Take the next K full batches' indices and start their upload into the next index slot
         (None at a ragged tail / the end of finite data)."""
         ta = time.perf_counter()
@@ -564,27 +512,14 @@ class FusedMnistTrainer:
         tb = time.perf_counter()
         if idx is None:
             return None
-        if not hasattr(self, "_stage"):
-            self._stage, self._stage_ev, self._slot = [None] * self._nslots, [None] * self._nslots, 0
-        slot = self._slot
-        self._slot = (slot + 1) % self._nslots
+        slot = self._ring.next_slot()
         graph, idx_buf, st = self._graph_for(K, handler.b, slot)
         tc = time.perf_counter()
-        self._upload(idx, idx_buf, slot)
+        self._ring.upload(idx, idx_buf, slot)
         self._last_take = (tb - ta, tc - tb, time.perf_counter() - tc)
         return (handler, K, idx.size // handler.b, graph, st)
 
-    def prefetch(self, handler: "DeviceHandler", K: int) -> bool:
-        """Input prefetch of depth one execution (tf.data ``prefetch`` semantics): take and upload
-        the indices of the next K-step execution now, so the next ``run_train`` launches its first
-        graph without waiting for the host's batch assembly.  Returns False at a ragged tail."""
-        K = min(int(K), self.K)
-        if self._ready is not None:
-            return self._ready[1] == K
-        self._ready = self._take_upload(handler, K)
-        return self._ready is not None
-
-    def run_train(self, handler: "DeviceHandler", steps: int) -> int:
+    def run_train(self, handler: EX.DeviceHandler, steps: int) -> int:
         # everything allocated so far (modules, model, graphs) is long-lived: move it out of the
         # cyclic GC's generations so a collection in the launch loop scans only per-step garbage
         # (a full collection of the torch-sized heap stalled the host ~30 ms mid-run)
@@ -592,17 +527,11 @@ class FusedMnistTrainer:
         done = 0
         b = handler.b
         opt = self.optimizer
-        if not hasattr(self, "_stage"):
-            self._stage, self._stage_ev, self._slot = [None] * self._nslots, [None] * self._nslots, 0
         timing = self._host_times is not None
         while done < steps:
             K = min(self.K, steps - done)
             t0 = time.perf_counter() if timing else 0.0
-            r, self._ready = self._ready, None
-            if r is not None and (r[0] is not handler or r[1] != K):
-                raise RuntimeError("fused trainer: prefetched execution does not match the requested steps")
-            if r is None:
-                r = self._take_upload(handler, K)
+            r = self._next_execution(handler, K)
             t1 = t2 = time.perf_counter() if timing else 0.0
             if r is None:
                 # ragged tail (end of finite data) -> eager steps of their own sizes
@@ -624,16 +553,15 @@ class FusedMnistTrainer:
             elif isinstance(graph, list):
                 for k, gk in enumerate(graph):
                     gk.replay()
-                    self._step_k = k
                     if opt.accumulate(self.G, k):  # (True when accumulation is off)
-                        self._reduce_and_update()
+                        self._reduce_and_update(k)
             elif graph is not None:
                 graph.replay()
             else:
                 for k in range(K):
                     self._train_step(st, k * b, b * self.R)
             if timing:
-                tk = getattr(self, "_last_take", (0.0, 0.0, 0.0)) if t1 - t0 > 1e-4 else (t1 - t0, 0.0, 0.0)
+                tk = self._last_take if t1 - t0 > 1e-4 else (t1 - t0, 0.0, 0.0)
                 self._host_times.append((tk[0], tk[1] + tk[2], time.perf_counter() - t2))
             opt.iterations += K
             done += K
@@ -643,16 +571,12 @@ class FusedMnistTrainer:
     def _eval_columns(self, lp, labels: bool):
         """Device copies of an evaluation pipeline's columns (the last one is cached), or None
         when they are not the reference model's input."""
-        cols = lp.columns if isinstance(lp.columns, (tuple, list)) else (lp.columns,)
-        x = cols[0]
-        y = cols[1] if len(cols) > 1 else None
-        if not isinstance(x, torch.Tensor) or tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28)) or \
-                x.dtype != torch.float32:
+        cols = _reference_columns(lp, labels)
+        if cols is None:
             return None
-        if labels and (not isinstance(y, torch.Tensor) or y.dim() != 1):
-            return None
-        key = _source_key(x, y if labels else None)
-        cached = getattr(self, "_eval_cache", None)
+        x, y = cols
+        key = _source_key(x, y)
+        cached = self._eval_cache
         if cached is None or not _same_source(cached[0], key):
             X = x.reshape(len(x), 28, 28, 1).to(self.device, torch.float32).contiguous()
             Y = (y.to(self.device, torch.int32) if labels else torch.zeros(len(x), dtype=torch.int32, device=self.device)).contiguous()
@@ -670,7 +594,7 @@ class FusedMnistTrainer:
         st._impl.set_metrics(metrics)
         return st
 
-    def _forward_batches(self, handler: "DeviceHandler", X, Y, cache, steps, metrics, logits_out=None):
+    def _forward_batches(self, handler: EX.DeviceHandler, X, Y, cache, steps, metrics, logits_out=None):
         """Forward-only passes over the handler's batches on the hand-written kernels."""
         K = 64
         done = 0
@@ -716,7 +640,7 @@ class FusedMnistTrainer:
         X, Y, cache = cols
         if lp.batch_size % self.R:
             return None
-        h = DeviceHandler(lp, None, self.rank, self.R)
+        h = EX.DeviceHandler(lp, None, self.rank, self.R)
         h._async = False
         metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
         try:
@@ -742,7 +666,7 @@ class FusedMnistTrainer:
         if cols is None:
             return None
         X, Y, cache = cols
-        h = DeviceHandler(lp, None, 0, 1)
+        h = EX.DeviceHandler(lp, None, 0, 1)
         h._async = False
         metrics = torch.zeros(4, dtype=torch.float32, device=self.device)
         out = []
@@ -800,118 +724,3 @@ class FusedMnistTrainer:
         self._xchg = None
         self.allreduce_mode = getattr(self.comm, "algorithm", self.comm.name)
 
-
-class _IndexProducer:
-    """Background thread producing the global-batch index arrays of an IndexStream into a bounded
-    queue, so an epoch's shuffle (native, GIL released) never stalls the launch loop."""
-
-    def __init__(self, stream: "DD.IndexStream", depth: int = 512):
-        self.stream = stream
-        self.q: "queue.Queue" = queue.Queue(maxsize=depth)
-        self._stop = threading.Event()
-        self._ended = False
-        self.t = threading.Thread(target=self._run, name="tdl-index-producer", daemon=True)
-        self.t.start()
-
-    def _run(self):
-        while not self._stop.is_set():
-            g = self.stream.next_batch()
-            item = (g, self.stream._epoch)  # epochs the stream had to generate to produce g
-            while not self._stop.is_set():
-                try:
-                    self.q.put(item, timeout=0.1)
-                    break
-                except queue.Full:
-                    continue
-            if g is None:
-                return
-
-    def get(self):
-        """(batch or None at the end, epochs generated up to it)."""
-        if self._ended:
-            return None, None
-        g, ep = self.q.get()
-        if g is None:
-            self._ended = True
-        return g, ep
-
-    def close(self):
-        self._stop.set()
-        while True:
-            try:
-                self.q.get_nowait()
-            except queue.Empty:
-                break
-        self.t.join(timeout=5)
-
-
-class DeviceHandler:
-    """Index vectors for this replica: its slice of every global batch."""
-
-    def __init__(self, lp: DD.LoweredPipeline, seed: Optional[int], rank: int, R: int):
-        self.lp = lp
-        self.rank, self.R = rank, R
-        self.B = lp.batch_size
-        self.b = lp.batch_size // R
-        self.stream = DD.IndexStream(lp, seed)
-        self._pending = []
-        self._async = os.environ.get("TDL_ASYNC_INDICES", "1") == "1"
-        self._producer: Optional[_IndexProducer] = None
-        self._epochs_used = 0
-
-    def new_iterator(self):
-        self.close()
-        self.stream = DD.IndexStream(self.lp, self.stream._seed)
-        self._pending = []
-        self._epochs_used = 0
-
-    def close(self):
-        if self._producer is not None:
-            self._producer.close()
-            self._producer = None
-        self.stream.commit(self._epochs_used)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _next_global(self):
-        if self._pending:
-            return self._pending.pop(0)
-        if not self._async:
-            g = self.stream.next_batch()
-            self._epochs_used = self.stream._epoch
-            return g
-        if self._producer is None:
-            self._producer = _IndexProducer(self.stream)
-        g, ep = self._producer.get()
-        if ep is not None:
-            self._epochs_used = ep
-        return g
-
-    def take(self, K: int) -> Optional[np.ndarray]:
-        """Up to K full global batches -> this replica's [K'*b] indices.  Stops early in front of
-        a partial batch (the epoch's remainder, left pending for ``next_ragged``) or the end of
-        finite data; None when the next batch is not a full one."""
-        got = []
-        for _ in range(K):
-            g = self._next_global()
-            if g is None or len(g) < self.B:
-                if g is not None:
-                    self._pending.insert(0, g)
-                break
-            got.append(g)
-        if not got:
-            return None
-        return np.concatenate([g[self.rank * self.b:(self.rank + 1) * self.b] for g in got])
-
-    def next_ragged(self):
-        g = self._next_global()
-        if g is None:
-            return None
-        sizes = input_lib.split_sizes(len(g), self.R)
-        lo = sum(sizes[: self.rank])
-        n = sizes[self.rank]
-        return g[lo:lo + n], n, len(g)

@@ -32,6 +32,7 @@ import torch
 
 from ..data import device as DD
 from ..parallel import input_lib
+from . import execution as EX
 from . import fused as F
 
 
@@ -89,7 +90,6 @@ class _ReplicaFused(F.FusedMnistTrainer):
             st.set_exchange(self.grp.xchg[self.r], twoshot=self.grp.twoshot)
 
     def _apply(self, st, global_b: int, k: int = 0):
-        self._step_k = k
         mode = self.grp.mode
         if mode == "xchg" and st.has_exchange:
             st.finalize(True, exchange=True, keep_grad=False)
@@ -101,7 +101,7 @@ class _ReplicaFused(F.FusedMnistTrainer):
                 ch.all_reduce_sgd(self.G, self.W, self.optimizer.lr_dev, 1.0)
             else:
                 ch.all_reduce(self.G, self.G, 1.0)
-                self._update()
+                self._update(k=k)
             return
         raise RuntimeError("mirrored fused trainer: no in-graph all-reduce in serial mode")
 
@@ -130,7 +130,7 @@ class _SliceHandler:
         return g[lo:lo + sizes[self.r]], sizes[self.r], len(g)
 
 
-class MirroredFusedTrainer:
+class MirroredFusedTrainer(EX.Prefetching):
     """See module docstring."""
 
     kind = "fused"
@@ -156,9 +156,6 @@ class MirroredFusedTrainer:
         self.xchg = self.ar = None
         self.allreduce_mode = None
         self.fallbacks: List[str] = []
-        self._nslots = self.subs[0]._nslots
-        self._slot = 0
-        self._ready = None
         self._data_key = None
         self._b = None
         self.broadcast_from_primary()
@@ -196,15 +193,12 @@ class MirroredFusedTrainer:
     # ------------------------------------------------------------------ data
     def prepare(self, dataset):
         lp = DD.lower(dataset)
-        if lp is None:
-            return None
-        cols = lp.columns if isinstance(lp.columns, (tuple, list)) else (None, None)
-        x, y = cols[:2]
-        if x is None or y is None or tuple(x.shape[1:]) not in ((28, 28, 1), (28, 28)) or \
-                x.dtype != torch.float32 or y.dim() != 1:
+        cols = F._reference_columns(lp)
+        if cols is None:
             return None
         if lp.batch_size % self.G:
             raise ValueError(f"global batch {lp.batch_size} is not divisible by {self.G} replicas")
+        x, y = cols
         key = F._source_key(x, y)
         if not F._same_source(self._data_key, key):
             per_dev = {}
@@ -218,7 +212,7 @@ class MirroredFusedTrainer:
                 s._steps, s._graphs = {}, {}
             self._data_key = key
         # ONE pipeline for the process (TF: the global batch is split over the local replicas)
-        h = F.DeviceHandler(lp, None, 0, 1)
+        h = EX.DeviceHandler(lp, None, 0, 1)
         self._b = lp.batch_size // self.G
         for s in self.subs:
             s._handlers_b = [self._b]
@@ -359,27 +353,17 @@ class MirroredFusedTrainer:
         if idx is None:
             return None
         Kr = idx.size // handler.b
-        slot = self._slot
-        self._slot = (slot + 1) % self._nslots
+        slot = self.subs[0]._ring.next_slot()  # (the same slot of every replica's ring)
         # every replica's graph exists before any of this execution is launched (a capture syncs
         # its device, which must never wait on a launched replica whose peers are not launched yet)
         ents = []
         for s in self.subs:
             with torch.cuda.device(s.device):
-                if not hasattr(s, "_stage"):
-                    s._stage, s._stage_ev, s._slot = [None] * s._nslots, [None] * s._nslots, 0
                 ents.append(s._graph_for(K, self._b, slot))
         for r, (s, sl) in enumerate(zip(self.subs, self._slices(idx, Kr))):
             with self.dc.on(r):
-                s._upload(sl, ents[r][1], slot)
+                s._ring.upload(sl, ents[r][1], slot)
         return handler, K, Kr, ents
-
-    def prefetch(self, handler, K: int) -> bool:
-        K = min(int(K), self.K)
-        if self._ready is not None:
-            return self._ready[1] == K
-        self._ready = self._take_upload(handler, K)
-        return self._ready is not None
 
     def run_train(self, handler, steps: int) -> int:
         gc.freeze()
@@ -388,11 +372,7 @@ class MirroredFusedTrainer:
         self._sync_optimizers()
         while done < steps:
             K = min(self.K, steps - done)
-            ent, self._ready = self._ready, None
-            if ent is not None and (ent[0] is not handler or ent[1] != K):
-                raise RuntimeError("mirrored fused trainer: prefetched execution does not match the requested steps")
-            if ent is None:
-                ent = self._take_upload(handler, K)
+            ent = self._next_execution(handler, K)
             if ent is None:
                 one = handler.next_ragged()
                 if one is None:
@@ -437,8 +417,7 @@ class MirroredFusedTrainer:
         self.dc.all_reduce([s.G for s in self.subs], "sum")
         for r, s in enumerate(self.subs):
             with self.dc.on(r):
-                s._step_k = k
-                s._update()
+                s._update(k=k)
 
     def _ragged_step(self, g: np.ndarray):
         """A partial global batch: split over the replicas, local gradients, group all-reduce
@@ -536,7 +515,7 @@ class MirroredFusedTrainer:
         cols = [s._eval_columns(lp, labels=True) for s in self.subs]
         if any(c is None for c in cols):
             return None
-        h = F.DeviceHandler(lp, None, 0, 1)
+        h = EX.DeviceHandler(lp, None, 0, 1)
         h._async = False
         batches = []
         try:

@@ -23,6 +23,7 @@ import torch
 
 from ..data import dataset as D
 from ..parallel import input_lib
+from . import execution as EX
 from .slab import transpose_tables
 from ..utils.tracing import trace_range
 
@@ -168,6 +169,11 @@ class GenericTrainer:
         self._graphs: Dict[tuple, tuple] = {}
         self._seen: Dict[tuple, int] = {}
         self._graph_ok: Optional[bool] = None
+        # device-resident executions (prepare()): the uploaded dataset's identity, the execution's index
+        # buffer and the pinned ring it is filled through, the batch size and the sizes that have run eagerly
+        self._dev_key = self._dev_idx = self._dev_b = None
+        self._dev_ring = EX.IndexRing(self.device, 4)
+        self._dev_warm = set()
         # metric accumulators start from zero for callers that drive run_train() directly
         # (fit() resets them per epoch; scripts/bench_resnet50.py did not, and reported stale state)
         self.reset_metrics()
@@ -493,17 +499,12 @@ class GenericTrainer:
             # gradient accumulation: the LOCAL gradient is folded into the optimizer's accumulator slab; only
             # the cycle's last micro-step goes on to the all-reduce (one, of the whole slab) and the update
             with torch.no_grad(), trace_range("tdl.accumulate"):
-                opt._zero_grad_after, opt._zeroed_grad = G.is_cuda, False
-                try:
-                    apply = opt.accumulate(G)
-                finally:
-                    opt._zero_grad_after = False
+                apply = opt.accumulate(G, zero_grad=G.is_cuda)
         if not apply:
             with torch.no_grad():
                 opt.iterations += 1
-                # (the accumulate kernel zeroed G after reading it)
-                self._g_clean = G.data_ptr() if opt._zeroed_grad else None
-                opt._zeroed_grad = False
+                # (on a GPU slab the accumulate kernel zeroed G after reading it, as asked)
+                self._g_clean = G.data_ptr() if G.is_cuda else None
                 if per_ex is not None:
                     self.loss_tracker.update_state(per_ex.detach())
                     yp = y_pred.detach()
@@ -531,20 +532,15 @@ class GenericTrainer:
                 else:
                     self.comm.all_reduce(G, "sum")
         with torch.no_grad(), trace_range("tdl.optimizer"):
-            opt._zero_grad_after, opt._zeroed_grad = G.is_cuda, False
-            try:
-                opt.apply_flat(self.W, G, sync_lr=sync_lr, t_add=t_add, accumulated=True)
-            finally:
-                opt._zero_grad_after = False
-            if opt._accumulating and G.is_cuda and not opt._zeroed_grad:
+            zeroed = opt.apply_flat(self.W, G, sync_lr=sync_lr, t_add=t_add, accumulated=True, zero_grad=G.is_cuda)
+            if opt._accumulating and G.is_cuda and not zeroed:
                 # the other micro-steps of a cycle leave G clean (the accumulate kernel zeroes it), so this one
                 # does too -- the fill the next step would start with -- and a captured step's choice between
                 # "G is clean" and "zero G first" never depends on which micro-step ran before the capture
                 G.zero_()
-                opt._zeroed_grad = True
+                zeroed = True
             # (only an optimizer kernel that zeroed G after reading it marks this slab clean)
-            self._g_clean = G.data_ptr() if opt._zeroed_grad else None
-            opt._zeroed_grad = False
+            self._g_clean = G.data_ptr() if zeroed else None
             if _ck.enabled():
                 _ck.record("slab_W", self.W)
             if per_ex is not None:  # (the fused loss head advanced the metric accumulators itself)
@@ -554,9 +550,7 @@ class GenericTrainer:
                     m.update_state(y, yp, sw)
 
     def run_train(self, handler, steps: int) -> int:
-        from .fused import DeviceHandler
-
-        if isinstance(handler, DeviceHandler):  # (prepare(): device-resident input, execution graphs)
+        if isinstance(handler, EX.DeviceHandler):  # (prepare(): device-resident input, execution graphs)
             return self._run_device(handler, steps)
         done = 0
         for _ in range(steps):
@@ -620,29 +614,13 @@ class GenericTrainer:
         p = opt._accum_phase()
         return "last" if p == opt.gradient_accumulation_steps - 1 else ("first" if p == 0 else "middle")
 
-    def _exec_key(self, K: int, b: int, t_add: int = 0) -> tuple:
-        """Key of the K-step execution graph at batch size b that starts ``t_add`` micro-steps from now; with
-        gradient accumulation it carries the execution's starting phase (every step's mode is baked in)."""
-        opt = self.optimizer
-        return ("dev", K, b, opt._accum_phase(t_add)) if opt._accumulating else ("dev", K, b)
-
     def _capture(self, batch, global_n: int):
         flat = D.flatten(batch)
         static = [torch.empty_like(t, device=self.device).copy_(t) for t in flat]
         it = iter(static)
         sbatch = D.map_structure(lambda _t: next(it), batch)
-        dev = self.device
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        it0 = self.optimizer.iterations
-        try:
-            with torch.cuda.graph(graph, stream=s):
-                self.train_step(sbatch, global_n, sync_lr=False)
-        finally:
-            self.optimizer.iterations = it0  # capture records, it does not run a step
-        torch.cuda.current_stream(dev).wait_stream(s)
+        with EX.capturing(self.device, self.optimizer) as graph:
+            self.train_step(sbatch, global_n, sync_lr=False)
         return static, graph
 
     # ------------------------------------------------------------------ device-resident executions
@@ -657,7 +635,6 @@ class GenericTrainer:
         if self.device.type != "cuda" or os.environ.get("TDL_GENERIC_DEVICE_DATA", "1") != "1":
             return None
         from ..data import device as DD
-        from . import fused as F
 
         lp = DD.lower(dataset)
         if lp is None or not isinstance(lp.columns, (tuple, list)) or len(lp.columns) != 2:
@@ -669,7 +646,7 @@ class GenericTrainer:
         if lp.batch_size % R or not self._graphable():  # (_graphable is collective at R > 1: every rank is here)
             return None
         key = (x.data_ptr(), tuple(x.shape), y.data_ptr(), tuple(y.shape), x._version, y._version)
-        if getattr(self, "_dev_key", None) != key:
+        if self._dev_key != key:
             self._X = x.to(self.device).contiguous()
             self._Y = y.to(self.device).contiguous()
             self._dev_key = key
@@ -680,29 +657,17 @@ class GenericTrainer:
                            self._X.data_ptr() % 16 == 0)
         policy = input_lib.effective_policy(dataset) if R > 1 else None
         seed = input_lib.shared_seed(self.strategy) if policy is not None and policy.name in ("DATA", "FILE") else None
-        return F.DeviceHandler(lp, seed, self.comm.rank, R)
+        return EX.DeviceHandler(lp, seed, self.comm.rank, R)
 
     def _dev_upload(self, idx) -> None:
         """The execution's sample ids into the device index buffer (stream-ordered after the previous
         execution's graph, which reads the same buffer), through a ring of pinned staging buffers."""
         n = int(idx.size)
-        if getattr(self, "_dev_idx", None) is None or self._dev_idx.numel() < n:
+        if self._dev_idx is None or self._dev_idx.numel() < n:
             self._dev_idx = torch.zeros(max(n, 1024), dtype=torch.int32, device=self.device)
             self._graphs = {k: v for k, v in self._graphs.items() if k[0] != "dev"}  # they read the old buffer
-            self._dev_stage = [None] * 4
-            self._dev_ev = [None] * 4
-            self._dev_slot = 0
-        s = self._dev_slot
-        self._dev_slot = (s + 1) % len(self._dev_stage)
-        if self._dev_stage[s] is None or self._dev_stage[s].numel() < n:
-            self._dev_stage[s] = torch.empty(self._dev_idx.numel(), dtype=torch.int32, pin_memory=True)
-        elif self._dev_ev[s] is not None:
-            self._dev_ev[s].synchronize()  # the copy out of this staging buffer has run
-        self._dev_stage[s][:n].numpy()[:] = idx
-        self._dev_idx[:n].copy_(self._dev_stage[s][:n], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self._dev_ev[s] = ev
+            self._dev_ring.reserve(self._dev_idx.numel())
+        self._dev_ring.upload(idx, self._dev_idx, self._dev_ring.next_slot())
 
     def _dev_step(self, k: int, b: int, global_n: int, sync_lr: bool):
         ii = self._dev_idx[k * b:(k + 1) * b]
@@ -717,20 +682,18 @@ class GenericTrainer:
     def warm_graphs(self, steps: int, b: Optional[int] = None):
         """Capture (without running) the execution graphs ``run_train(steps)`` will replay, once a
         step of this batch size has run eagerly (bench.py: ahead of the timed region)."""
-        b = b if b is not None else getattr(self, "_dev_b", None)
-        if b is None or b not in getattr(self, "_dev_warm", ()) or self._graph_ok is False:
+        b = b if b is not None else self._dev_b
+        if b is None or b not in self._dev_warm or self._graph_ok is False:
             return
-        K = max(1, self.model._steps_per_execution)
-        sizes = ({K} if steps >= K else set()) | ({steps % K} if steps % K else set())
-        if getattr(self, "_dev_idx", None) is None or self._dev_idx.numel() < max(sizes) * b:
-            self._dev_upload(np.zeros(max(sizes) * b, dtype=np.int32))
         # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
-        a = self.optimizer.gradient_accumulation_steps if self.optimizer._accumulating else 1
-        starts = [(K, i * K) for i in range(min(steps // K, a))]
-        if steps % K:
-            starts.append((steps % K, steps - steps % K))
+        opt = self.optimizer
+        starts = EX.execution_starts(steps, max(1, self.model._steps_per_execution),
+                                     opt.gradient_accumulation_steps or 1)
+        n = max(k for k, _ in starts) * b
+        if self._dev_idx is None or self._dev_idx.numel() < n:
+            self._dev_upload(np.zeros(n, dtype=np.int32))
         for k, t_add in starts:
-            if self._exec_key(k, b, t_add) not in self._graphs:
+            if EX.accum_key(opt, ("dev", k, b), t_add) not in self._graphs:
                 self._dev_capture(k, b, t_add)
 
     def _run_device(self, handler, steps: int) -> int:
@@ -739,8 +702,6 @@ class GenericTrainer:
         gc.freeze()  # long-lived state out of the cyclic GC's generations (engine/fused.py run_train)
         done, b, opt = 0, handler.b, self.optimizer
         self._dev_b = b
-        if not hasattr(self, "_dev_warm"):
-            self._dev_warm = set()
         spe = max(1, self.model._steps_per_execution)
         while done < steps:
             idx = handler.take(min(spe, steps - done))
@@ -759,7 +720,7 @@ class GenericTrainer:
             K = idx.size // b
             self._dev_upload(idx)
             opt._sync_lr()
-            graph = self._graphs.get(self._exec_key(K, b))
+            graph = self._graphs.get(EX.accum_key(opt, ("dev", K, b)))
             if (graph is None and b in self._dev_warm and self._graph_ok is not False and
                     os.environ.get("TDL_GENERIC_DEVICE_EAGER", "0") != "1"):
                 graph = self._dev_capture(K, b)
@@ -780,28 +741,18 @@ class GenericTrainer:
     def _dev_capture(self, K: int, b: int, t_add: int = 0):
         """Capture the K-step execution that starts ``t_add`` micro-steps from now (only its accumulation
         phase depends on the start: the step count the kernels read is on the device)."""
-        dev = self.device
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(dev)
-        s.wait_stream(torch.cuda.current_stream(dev))
-        it0 = self.optimizer.iterations
-        key = self._exec_key(K, b, t_add)
-        self.optimizer.iterations = it0 + t_add
+        key = EX.accum_key(self.optimizer, ("dev", K, b), t_add)
         try:
-            with torch.cuda.graph(graph, stream=s):
+            with EX.capturing(self.device, self.optimizer, t_add) as graph:
                 for k in range(K):
                     self._dev_step(k, b, b * self.comm.world_size, sync_lr=False)
         except Exception as e:  # noqa: BLE001 - a layer with host-side logic: stay eager
             import warnings
 
             warnings.warn(f"execution graph capture failed, training eagerly: {type(e).__name__}: {e}")
-            torch.cuda.synchronize(dev)
+            torch.cuda.synchronize(self.device)
             self._graph_ok = False
             return None
-        finally:
-            self.optimizer.iterations = it0  # capture records, it does not run a step
-        torch.cuda.current_stream(dev).wait_stream(s)
         self._graphs[key] = graph
         return graph
 

@@ -107,11 +107,15 @@ class Optimizer:
 
     _needs_step = False  # the device update reads t_dev (Adam's bias correction)
 
-    def device_update(self, W: torch.Tensor, G: torch.Tensor, t_add: int = 0) -> bool:
+    _update_zeroes_grad = False  # the device update kernel can zero G once it has read it (``zero_grad``)
+
+    def device_update(self, W: torch.Tensor, G: torch.Tensor, t_add: int = 0, zero_grad: bool = False) -> bool:
         """One hand-written flat-slab update kernel (learning rate and step count read from the
         device: capturable) when this optimizer has one and the slab is on the GPU; False
         otherwise (the caller then uses apply_flat).  ``t_add``: the step's offset inside an
-        execution whose first step is t_dev (Adam)."""
+        execution whose first step is t_dev (Adam).  ``zero_grad``: the generic trainer's request to
+        zero G after its use, so its next step needs no fill launch; only a kernel of an optimizer
+        with ``_update_zeroes_grad`` honours it, the others ignore it."""
         return False
 
     def set_layout(self, layout):
@@ -197,7 +201,7 @@ class Optimizer:
         host knows it at launch and at capture time (no device counter)."""
         return (int(self.iterations) + int(t_add)) % self.gradient_accumulation_steps
 
-    def accumulate(self, G: torch.Tensor, t_add: int = 0) -> bool:
+    def accumulate(self, G: torch.Tensor, t_add: int = 0, zero_grad: bool = False) -> bool:
         """The fold of one micro-step over the gradient slab ``G`` into the slot ``"gradient_accumulator"``
         (``A``), by the phase p of the micro-step (``t_add``: its offset inside an execution whose first step is
         ``iterations``), every operation one f32 rounding:
@@ -207,8 +211,8 @@ class Optimizer:
         Returns whether this is the apply micro-step (p == k-1): ``G`` then holds the mean gradient of the cycle
         and the caller all-reduces, clips and updates as an unaccumulated step would.  On a GPU slab it is one
         ``_C.grad_accum`` launch (csrc/kernels/accum.hip; capturable, the mode is baked in at capture), which
-        also zeroes ``G`` on the other micro-steps when the trainer asked for it (``_zero_grad_after``); the
-        torch formulas are the CPU implementation.  A no-op returning True when accumulation is off."""
+        also zeroes ``G`` on the other micro-steps when the trainer asked for it (``zero_grad``); the
+        torch formulas, the CPU implementation, never do.  A no-op returning True when accumulation is off."""
         if not self._accumulating:
             return True
         if self._n != G.numel() or self._device != G.device:
@@ -224,10 +228,7 @@ class Optimizer:
             if G.dtype != torch.float32 or not hasattr(ops.hip(), "grad_accum"):
                 raise RuntimeError("gradient accumulation: the extension has no grad_accum kernel for the GPU slab "
                                    "(rebuild: python build_native.py)")
-            zero = mode != 2 and bool(getattr(self, "_zero_grad_after", False))
-            ops.hip().grad_accum(G, A, mode, c, zero_grad=zero)
-            if zero:
-                self._zeroed_grad = True
+            ops.hip().grad_accum(G, A, mode, c, zero_grad=bool(zero_grad) and mode != 2)
         elif mode == 0:
             A.copy_(G)
         elif mode == 1:
@@ -238,27 +239,29 @@ class Optimizer:
         return mode == 2
 
     def apply_flat(self, W: torch.Tensor, G: torch.Tensor, sync_lr: bool = True, t_add: int = 0,
-                   accumulated: bool = False):
+                   accumulated: bool = False, zero_grad: bool = False) -> bool:
         """w <- update(w, g) over the whole slab (gradients already all-reduced).  ``t_add``: this
         step's offset from ``t_dev`` inside a multi-step execution (only Adam reads a step count).
         With gradient accumulation on, ``G`` is first folded (``accumulate``) unless the caller has done so
-        (``accumulated=True``); a micro-step that is not the cycle's last only counts."""
+        (``accumulated=True``); a micro-step that is not the cycle's last only counts.  Returns whether the
+        update kernel zeroed ``G`` after reading it, as ``zero_grad`` asked (see ``device_update``)."""
         if self._n != W.numel() or self._device != W.device:
             self.build(W.numel(), W.device)
         if self._accumulating and not accumulated and not self.accumulate(G):
             self.iterations += 1
-            return
+            return False
         if sync_lr:
             self._sync_lr()
-        if self.device_update(W, G, t_add):  # clip + (decay +) update in the kernel
+        if self.device_update(W, G, t_add, zero_grad=zero_grad):  # clip + (decay +) update in the kernel
             self.iterations += 1
-            return
+            return bool(zero_grad) and self._update_zeroes_grad
         self._clip(G)
         if self.weight_decay:
             W.mul_(1.0 - self.current_lr() * self.weight_decay)
         with torch.no_grad():
             self._update(W, G)
         self.iterations += 1
+        return False
 
     def _update(self, W, G):
         raise NotImplementedError
@@ -368,6 +371,7 @@ class SGD(Optimizer):
     # the GPU update reads the learning rate from ``lr_dev`` (refreshed before every step), so a
     # captured step graph stays correct under learning-rate schedules
     graph_safe = True
+    _update_zeroes_grad = True  # (k_sgd / k_sgd_momentum take zero_grad)
 
     def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, name="SGD", **kw):
         super().__init__(learning_rate, name, **kw)
@@ -378,21 +382,18 @@ class SGD(Optimizer):
     def _slot_names(self):
         return ["momentum"] if self.momentum > 0 else []
 
-    def device_update(self, W, G, t_add=0):
+    def device_update(self, W, G, t_add=0, zero_grad=False):
         if not _hip_ok(W, "sgd", self) or self.weight_decay:
             return False
         from .. import ops
 
         C = ops.hip()
         clip = self.device_clip(G)
-        # (the generic trainer's request: zero G after its use, so its next step needs no fill launch)
-        zero = bool(getattr(self, "_zero_grad_after", False))
         if self.momentum > 0:
-            C.sgd_momentum(W, G, self._slots["momentum"], self.lr_dev, self.momentum, self.nesterov, zero_grad=zero,
-                           **clip)
+            C.sgd_momentum(W, G, self._slots["momentum"], self.lr_dev, self.momentum, self.nesterov,
+                           zero_grad=bool(zero_grad), **clip)
         else:
-            C.sgd(W, G, self.lr_dev, zero_grad=zero, **clip)
-        self._zeroed_grad = zero
+            C.sgd(W, G, self.lr_dev, zero_grad=bool(zero_grad), **clip)
         return True
 
     def _update(self, W, G):
@@ -431,7 +432,7 @@ class Adam(Optimizer):
 
     _needs_step = True
 
-    def device_update(self, W, G, t_add=0):
+    def device_update(self, W, G, t_add=0, zero_grad=False):
         """csrc/kernels/optim.hip k_adam (AdamW's decoupled decay inside the same pass)."""
         if not _hip_ok(W, "adam", self):
             return False
@@ -477,7 +478,7 @@ class RMSprop(Optimizer):
     # (the torch fallback bakes lr; clipping: see Adam.graph_safe)
     graph_safe = property(lambda self: self._clip_on_device and _kernel_present("rmsprop"))
 
-    def device_update(self, W, G, t_add=0):
+    def device_update(self, W, G, t_add=0, zero_grad=False):
         """csrc/kernels/optim.hip k_rmsprop."""
         if not _hip_ok(W, "rmsprop", self) or self.weight_decay:
             return False
@@ -523,7 +524,7 @@ class Adagrad(Optimizer):
 
     graph_safe = property(lambda self: self._clip_on_device and _kernel_present("adagrad"))
 
-    def device_update(self, W, G, t_add=0):
+    def device_update(self, W, G, t_add=0, zero_grad=False):
         """csrc/kernels/optim.hip k_adagrad."""
         if not _hip_ok(W, "adagrad", self) or self.weight_decay:
             return False
@@ -624,7 +625,7 @@ class _Layerwise(Optimizer):
         (see Adam.graph_safe)."""
         return self._tables is not None and self._clip_on_device
 
-    def device_update(self, W, G, t_add=0):
+    def device_update(self, W, G, t_add=0, zero_grad=False):
         """csrc/kernels/layerwise.hip: chunk sums, per-variable ratios, update."""
         if W.device.type != "cuda" or W.dtype != torch.float32:
             return False

@@ -86,11 +86,11 @@ def test_engine_fold_and_update_are_exact(fused):
     def hook(model, opt):
         inner = opt.accumulate
 
-        def accumulate(G, t_add=0):
+        def accumulate(G, t_add=0, **kw):  # (kw: the generic trainer's zero_grad request)
             if not first_w:
                 first_w.append(model._W.clone())
             local.append(G.clone())
-            last = inner(G, t_add)
+            last = inner(G, t_add, **kw)
             if last:
                 folded.append(G.clone())
             return last
