@@ -25,8 +25,10 @@ __device__ __forceinline__ f4 zero4() { return f4{0.f, 0.f, 0.f, 0.f}; }
 // two f32 -> packed bf16 (lo in bits 0-15), round to nearest even: one v_cvt_pk_bf16_f32 (the same bits
 // as the integer RNE `u + 0x7fff + lsb` sequence for finite values, at a fraction of its VALU cost; a NaN
 // stays a NaN whatever its payload, where the integer sequence carries out of it into Inf or +-0).
-// conv.hip, conv_wgrad.hip, wgrad3x3.hip and stem.hip keep the integer sequence on purpose: what they
-// round are sums of products of bf16 inputs, whose NaN payloads have zero low bits and cannot carry.
+// conv.hip, conv_wgrad.hip, wgrad3x3.hip and the epilogue and reduce of stem.hip keep the integer sequence
+// on purpose: what they round are sums of products of bf16 inputs, whose NaN payloads have zero low bits
+// and cannot carry.  stem.hip's pack kernel rounds the caller's f32 image, whose NaNs can carry any
+// payload, and uses this function.
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   typedef float f2_t __attribute__((ext_vector_type(2)));
   typedef __bf16 b2_t __attribute__((ext_vector_type(2)));

@@ -40,12 +40,14 @@ constexpr int kTaps = 32;  // 8 filter columns x 4 channels per filter row
 
 __device__ __forceinline__ uint16_t f2bf(float f) {
   uint32_t u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even (finite values)
+  u += 0x7fffu + ((u >> 16) & 1u);  // round to nearest even (finite values, and NaNs of bf16 arithmetic)
   return (uint16_t)(u >> 16);
 }
 
 // x [N][H][W][C] (f32 or bf16) -> xp [N][HP][WP][4] bf16: pixel (h, w) of x at (h + PT, w + PL),
-// zeros elsewhere and in channels C..3.  One thread per xp pixel (one 8-byte store).
+// zeros elsewhere and in channels C..3.  One thread per xp pixel (one 8-byte store).  An f32 pixel is
+// the caller's data, so its NaN can carry any payload: it is rounded with pack_bf16x2 (a NaN stays a
+// NaN), not with f2bf, which would carry out of the payload into Inf or +-0.
 template <typename T>
 __global__ __launch_bounds__(256) void k_stem_pack(const T* __restrict__ x, uint2* __restrict__ xp, int N, int H,
                                                    int W, int C, int HP, int WP, int PT, int PL) {
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(256) void k_stem_pack(const T* __restrict__ x, uint
         if constexpr (sizeof(T) == 2)
           v[c] = reinterpret_cast<const uint16_t*>(s)[c];
         else
-          v[c] = f2bf((float)s[c]);
+          v[c] = (uint16_t)pack_bf16x2((float)s[c], 0.f);
       }
     }
     xp[p] = make_uint2(v[0] | ((uint32_t)v[1] << 16), v[2] | ((uint32_t)v[3] << 16));

@@ -764,8 +764,10 @@ std::vector<at::Tensor> stem_fwd(at::Tensor x, at::Tensor w_hwio, int64_t pt, in
   TORCH_CHECK(tdl::stem_supported(C, KH, KW, (int)sw, K) && sh >= 1 && pt >= 0 && pb >= 0 && pl >= 0 && pr >= 0,
               "stem: unsupported geometry");
   const int HP = H + (int)(pt + pb), WPv = W + (int)(pl + pr);
+  // (a padded image smaller than the filter has no output: the division below truncates toward zero
+  // and would count one)
+  TORCH_CHECK(N > 0 && HP >= KH && WPv >= KW, "stem: empty output");
   const int OH = (HP - KH) / (int)sh + 1, OW = (WPv - KW) / 2 + 1;
-  TORCH_CHECK(OH > 0 && OW > 0, "stem: empty output");
   // packed width: every receptive field reads 8 columns (taps past KW are zero-weighted): 2(OW-1)+8
   const int WP = std::max(WPv, 2 * (OW - 1) + 8);
   const int HPp = std::max(HP, (OH - 1) * (int)sh + KH);
@@ -794,7 +796,8 @@ at::Tensor stem_wgrad(at::Tensor xp, at::Tensor dy, int64_t kh, int64_t kw, int6
   TORCH_CHECK(xp.dim() == 4 && xp.size(3) == 4 && dy.dim() == 4 && dy.size(0) == xp.size(0), "stem_wgrad: shapes");
   const int N = (int)xp.size(0), HP = (int)xp.size(1), WP = (int)xp.size(2);
   const int OH = (int)dy.size(1), OW = (int)dy.size(2), K = (int)dy.size(3);
-  TORCH_CHECK(tdl::stem_supported((int)c, (int)kh, (int)kw, 2, K) && (OH - 1) * sh + kh <= HP &&
+  TORCH_CHECK(tdl::stem_supported((int)c, (int)kh, (int)kw, 2, K) && sh >= 1 && N > 0 && OH > 0 && OW > 0 &&
+                  (OH - 1) * sh + kh <= HP &&
                   2 * (OW - 1) + 8 <= WP,
               "stem_wgrad: geometry inconsistent with the packed image");
   const int M = N * OH * OW;

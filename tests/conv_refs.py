@@ -1,6 +1,6 @@
 """f64 references of the bf16 implicit-GEMM convolution family (csrc/kernels/conv.hip, conv_wgrad.hip,
-wgrad3x3.hip), shared by test_conv_refs_cpu.py, test_conv_edges_gpu.py and test_conv_wgrad_edges_gpu.py.
-numpy only; nothing here touches a GPU.
+wgrad3x3.hip, stem.hip), shared by test_conv_refs_cpu.py, test_conv_edges_gpu.py,
+test_conv_wgrad_edges_gpu.py and test_stem_edges_gpu.py.  numpy only; nothing here touches a GPU.
 
 Tensors are NHWC; weights come in the kernels' own layouts (OHWI forward, HWIO gradients).  Every
 convolution is a loop over filter taps with one einsum per tap, so the indexing is the definition:
@@ -228,6 +228,33 @@ def dgrad_s2_epilogue_ref(acc, h, w, bm, res_bits=None, bn_y_bits=None, bn_x_bit
         if bn_x2_bits is not None:
             part2 = block_sums(bn_x2_bits)
     return v, part, part2
+
+
+# ------------------------------------------------------------------------------------- stem (stem.hip)
+def stem_geometry(H, W, KH, KW, SH, pads):
+    """(OH, OW, HPp, WP) of the small-channel conv with column stride 2 and pads (top, bottom, left, right):
+    the output size of the padded image, and the packed image's rows and columns.  Every output pixel's
+    window is 8 columns wide whatever KW is, so the packed row reaches column 2 (OW - 1) + 7 at the least;
+    the packed image has the rows the last output row reads.  (An image smaller than the filter: OH or
+    OW <= 0 by the floor division.)"""
+    pt, pb, pl, pr = pads
+    OH = (H + pt + pb - KH) // SH + 1
+    OW = (W + pl + pr - KW) // 2 + 1
+    WP = max(W + pl + pr, 2 * (OW - 1) + 8)
+    HPp = max(H + pt + pb, (OH - 1) * SH + KH)
+    return OH, OW, HPp, WP
+
+
+def stem_pack_ref(x, is_f32, KH, KW, SH, pads):
+    """uint16 bits of the packed image xp [N][HPp][WP][4] of x [N,H,W,C] (is_f32: f32 values, rounded with
+    bf16_rne -- a NaN of any payload stays a NaN; else bf16 bits, copied): pixel (h, w) at (h + pt, w + pl),
+    zero bits in the border and in channels C..3."""
+    x = np.asarray(x, np.float32 if is_f32 else np.uint16)
+    N, H, W, C = x.shape
+    _, _, HPp, WP = stem_geometry(H, W, KH, KW, SH, pads)
+    xp = np.zeros((N, HPp, WP, 4), np.uint16)
+    xp[:, pads[0]:pads[0] + H, pads[2]:pads[2] + W, :C] = bf16_rne(x) if is_f32 else x
+    return xp
 
 
 # ------------------------------------------------------------------------------------- data and bounds

@@ -166,3 +166,68 @@ def test_error_bound_is_the_derived_one():
     np.testing.assert_array_equal(CR.error_bound(r, ab, 576), 0.5 * R.ulp_bf16(np.abs(r) + e) + e)
     with pytest.raises(AssertionError):
         CR.assert_exact(np.array([2.0 ** 24]))
+
+
+# ------------------------------------------------------------------------------------- stem references
+def _stem_geoms():
+    rng = np.random.RandomState(11)
+    out = [(224, 224, 7, 7, 2, (3, 3, 3, 3)), (9, 9, 1, 1, 1, (0, 0, 0, 0)), (16, 37, 3, 5, 2, (0, 1, 2, 0)),
+           (20, 23, 8, 8, 3, (1, 2, 0, 1)), (6, 6, 7, 7, 2, (0, 0, 0, 0)), (7, 7, 7, 8, 2, (0, 0, 0, 0))]
+    while len(out) < 60:
+        out.append((rng.randint(1, 20), rng.randint(1, 20), rng.randint(1, 9), rng.randint(1, 9), rng.randint(1, 4),
+                    tuple(int(p) for p in rng.randint(0, 4, 4))))
+    return out
+
+
+@pytest.mark.parametrize("g", _stem_geoms())
+def test_stem_geometry_counts_the_valid_window_positions(g):
+    H, W, KH, KW, SH, pads = g
+    OH, OW, HPp, WP = CR.stem_geometry(H, W, KH, KW, SH, pads)
+    HP, WPv = H + pads[0] + pads[1], W + pads[2] + pads[3]
+    # brute force: window positions at multiples of the stride that lie inside the padded image
+    assert max(OH, 0) == sum(1 for t in range(0, HP, SH) if t + KH <= HP)
+    assert max(OW, 0) == sum(1 for l in range(0, WPv, 2) if l + KW <= WPv)
+    if OH <= 0 or OW <= 0:
+        return
+    # the packed image: the smallest that holds the padded image and every KH x 8 window the kernels read
+    assert HPp == max(HP, max(oh * SH + KH for oh in range(OH)))
+    assert WP == max(WPv, max(2 * ow + 8 for ow in range(OW)))
+    assert HPp == HP  # (the last window lies inside the padded image: extra rows need a taller filter than image)
+
+
+def test_stem_geometry_of_an_image_smaller_than_its_filter():
+    assert CR.stem_geometry(6, 20, 7, 7, 2, (0, 0, 0, 0))[0] == 0   # (C division would give (6 - 7) / 2 + 1 = 1)
+    assert CR.stem_geometry(20, 5, 7, 7, 2, (0, 0, 0, 1))[1] == 0
+
+
+@pytest.mark.parametrize("is_f32", [True, False])
+@pytest.mark.parametrize("g", [(2, 5, 6, 3, 7, 7, 2, (3, 3, 3, 3)), (1, 4, 9, 4, 2, 8, 1, (0, 1, 2, 0)),
+                               (2, 3, 4, 1, 3, 3, 3, (1, 0, 0, 2)), (1, 6, 5, 2, 1, 1, 1, (0, 0, 0, 0))])
+def test_stem_pack_ref_against_a_loop_per_pixel(g, is_f32):
+    N, H, W, C, KH, KW, SH, pads = g
+    rng = np.random.RandomState(H * W)
+    xf = (rng.randn(N, H, W, C) * 3).astype(np.float32)
+    x = xf if is_f32 else R.bf16_rne(xf)
+    got = CR.stem_pack_ref(x, is_f32, KH, KW, SH, pads)
+    OH, OW, HPp, WP = CR.stem_geometry(H, W, KH, KW, SH, pads)
+    assert got.shape == (N, HPp, WP, 4) and got.dtype == np.uint16
+    for n in range(N):
+        for hp in range(HPp):
+            for wp in range(WP):
+                h, w = hp - pads[0], wp - pads[2]
+                for c in range(4):
+                    want = 0
+                    if 0 <= h < H and 0 <= w < W and c < C:
+                        want = int(R.bf16_rne(xf[n, h, w, c:c + 1])[0])
+                    assert got[n, hp, wp, c] == want, (n, hp, wp, c)
+
+
+def test_stem_pack_ref_keeps_nan_payloads_and_copies_bf16_bits():
+    x = np.zeros((1, 1, 3, 2), np.float32)
+    x[0, 0, :, 0], x[0, 0, :, 1] = R.NAN_PAYLOADS_F32, -R.NAN_PAYLOADS_F32
+    xp = CR.stem_pack_ref(x, True, 1, 1, 1, (0, 0, 1, 0))
+    assert list(xp[0, 0, 1:4, 0]) == [0x7FC0, 0x7FFF, 0xFFFF]  # quieted, sign kept: never Inf, -0 or +0
+    assert R.bf16_is_nan(xp[0, 0, 1:4, :2]).all() and not xp[0, 0, 0].any() and not xp[..., 2:].any()
+    assert list(xp[0, 0, 1:4, 1] >> 15) == [1, 1, 0]
+    bits = np.array([0x7F81, 0xFFFF, 0x0001, 0x8000, 0x7F80], np.uint16).reshape(1, 1, 5, 1)  # signalling NaN, ...
+    assert np.array_equal(CR.stem_pack_ref(bits, False, 1, 1, 1, (0, 0, 0, 0))[0, 0, :5, 0], bits.ravel())
