@@ -12,9 +12,23 @@
 //                  stored transposed (trans_out) into dW HWIO [R S C][K]
 // Long reductions split over blockIdx.z into a partial-sum workspace reduced in a fixed order by a
 // second kernel (deterministic, no atomics).
+//
+// Non-finite values (pinned by tests/test_gemm_f32_edges_gpu.py and tests/test_conv_f32_edges_gpu.py):
+//   * The products and sums are IEEE f32: a NaN or Inf operand element reaches exactly the outputs whose
+//     reduction contains it (Inf * 0 = NaN included); padding taps and elements past a tile edge are not
+//     read, so they contribute an exact 0 whatever lies in memory there.
+//   * The ReLU epilogue (act = 1) is fmaxf(v, 0): a NaN pre-activation is stored as 0, not as NaN (the
+//     same deviation from max(v, 0) as bn.h's fused ReLU); -0 may be stored as either zero.
+//   * The pooled epilogue takes v > best from -inf, first maximum winning: a NaN never wins a window; a
+//     window of NaNs only (reachable with act = 0) stores -inf and argmax 255, as pool.hip's kernels do.
+//   * amask / bmask and the pooled-gradient routing are selects (mask > 0 ? operand : 0), not products: a
+//     masked Inf or NaN operand contributes 0, and a NaN mask masks (NaN > 0 is false).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <string>
+#include <vector>
 
 namespace tdl {
 
@@ -61,7 +75,9 @@ struct F32GemmArgs {
   float* pout = nullptr;
   uint8_t* parg = nullptr;
   int plan_m = 0;  // > 0: the split plan of an M = plan_m problem (the pooled conv takes the unfused conv's
-                   // reduction split, so its partial sums -- and outputs -- are bit-identical to it)
+                   // reduction split, so its partial sums -- and outputs -- are bit-identical to it WHEN that
+                   // plan has < 16 slices; with 16 or more the pooled conv reduces in one slice instead (see
+                   // f32_gemm_plan) and agrees with the unfused conv to f32 rounding only)
   // kF32ConvDgrad / kF32ConvWgrad with the output gradient given POOLED (the backward of that fused
   // forward): a = the pool's output gradient [N][PH][PW][K], amask = the pooled maximum, pin_arg = its
   // window positions; the conv-output gradient the loader forms is, at pixel (oy, ox) of the g.oh x g.ow
@@ -102,8 +118,39 @@ inline void f32_gemm_plan(F32GemmArgs& a, int kmin = 64, int cap = 1024) {
   }
 }
 
-void f32_gemm_launch(int mode, const F32GemmArgs& a, hipStream_t s);
-// many-slice reductions over >= 8192 outputs: 16 outputs per wave (default) or one (A/B hook)
-void f32_reduce16(bool on);
+// The kernels a launch takes: the k_gemm_f32<MODE, MA, MB, VA, VB, PIN, BUF> instantiation and the
+// split-reduce kernel behind it.  f32_gemm_launch dispatches on exactly this, so tests can read it.
+enum F32Reduce {
+  kF32ReduceNone = 0, kF32Reduce4, kF32Reduce8, kF32Reduce16, kF32ReduceWave, kF32ReduceWave4V4, kF32ReduceWave4S,
+  kF32ReduceWave16V4, kF32ReduceWave16S, kF32ReducePool4, kF32ReducePool8, kF32ReducePool16, kF32ReducePoolRows,
+  kF32ReduceCount
+};
+struct F32Selected {
+  int mode = 0;
+  bool ma = false, mb = false, va = false, vb = false, pin = false, buf = false;
+  int reduce = kF32ReduceNone;
+  int splits = 1, kchunk = 16;
+  // e.g. "dgrad_ma1_va1_vb0_pin0_buf1": the mode and the template flags that mode dispatches on
+  std::string main_name() const;
+  const char* reduce_name() const;
+};
+// pure host code (reads the pointers' nullness and the hooks below, dereferences nothing)
+F32Selected f32_gemm_selected(int mode, const F32GemmArgs& a);
+// every main and reduce name f32_gemm_selected can return, and only those (not the instantiated kernels it
+// never selects: a weight gradient with VA, a pooled gradient with BUF)
+std::vector<std::string> f32_kernel_names();
+
+// launches what f32_gemm_selected(mode, a) names, and returns it
+F32Selected f32_gemm_launch(int mode, const F32GemmArgs& a, hipStream_t s);
+// A/B hooks (each starts from its environment variable, unset = on).  Every setter returns the value it
+// replaced, so a caller can put it back:
+// many-slice reductions over >= 256 outputs: 4 / 16 outputs per wave (default) or one  [TDL_F32_REDUCE16]
+bool f32_reduce16(bool on);
+// operand loads through buffer resources where the operands fit (default), or 64-bit addresses  [TDL_F32_BUF]
+bool f32_buf(bool on);
+// few-slice reduces issue only the loads 4 / 8 slices need (default), or always 16  [TDL_F32_REDUCE_NARROW]
+bool f32_reduce_narrow(bool on);
+// pooled reduce: a window's partials loaded before any store (default), or row by row  [TDL_F32_POOLRED_HOIST]
+bool f32_pool_hoist(bool on);
 
 }  // namespace tdl

@@ -687,117 +687,199 @@ __global__ __launch_bounds__(256) void k_gemm_f32_reduce_wave16(F32GemmArgs a) {
   }
 }
 
-// TDL_F32_REDUCE16=0: every many-slice reduction one wave per output (A/B hook)
-bool g_reduce16 = [] {
-  const char* e = std::getenv("TDL_F32_REDUCE16");
+// A/B hooks, each from its environment variable until the run-time setter changes it (unset = on):
+bool env_on(const char* name) {
+  const char* e = std::getenv(name);
   return e == nullptr || std::atoi(e) != 0;
-}();
+}
+// TDL_F32_REDUCE16=0: every many-slice reduction one wave per output
+bool g_reduce16 = env_on("TDL_F32_REDUCE16");
+// TDL_F32_BUF=0: the 64-bit address form of the operand loaders everywhere
+bool g_buf = env_on("TDL_F32_BUF");
+// TDL_F32_REDUCE_NARROW=0: the few-slice reduces issue 16 loads whatever the slice count
+bool g_reduce_narrow = env_on("TDL_F32_REDUCE_NARROW");
+// TDL_F32_POOLRED_HOIST=0: the pooled reduce row by row
+bool g_pool_hoist = env_on("TDL_F32_POOLRED_HOIST");
 
-bool reduce16_on() { return g_reduce16; }
-
-// TDL_F32_REDUCE_NARROW=0: the few-slice reduces issue 16 loads whatever the slice count (A/B hook)
-bool reduce_narrow() {
-  static const bool on = [] {
-    const char* e = std::getenv("TDL_F32_REDUCE_NARROW");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  return on;
+// buffer-resource operand loads when both operands (and their masks) fit 32-bit byte offsets
+bool f32_buf_ok(const F32GemmArgs& a) {
+  return g_buf && a.na > 0 && a.nb > 0 && a.na < (int64_t(1) << 29) && a.nb < (int64_t(1) << 29);
 }
 
-// the operand-vectorisation instantiation of a (mode, mask) kernel
+const char* const kModeNames[4] = {"gemm", "fwd", "dgrad", "wgrad"};
+const char* const kReduceNames[kF32ReduceCount] = {
+    "none", "reduce4", "reduce8", "reduce16", "wave", "wave16x4_v4", "wave16x4_s", "wave16x16_v4", "wave16x16_s",
+    "pool4", "pool8", "pool16", "pool_rows"};
+
+// the instantiation of F32Selected k: one template level per flag the mode dispatches on.
+// f32_gemm_selected never sets va for the weight gradient (its A is not 16-B loaded) nor buf for the pooled
+// gradient, so those 18 kernels are never launched and f32_kernel_names() does not list them.  They are
+// instantiated all the same (plain ifs below, not if constexpr): without them every other kernel is the
+// same code at another address of the code object, and the generic engine's step measures 1.0 % slower
+// (profiles/f32_selection_ab.txt).  TODO: find out why the placement matters (instruction-cache sets?
+// the code object's page layout?) and drop the 18 once it no longer does; nothing else needs them.
 template <int MODE, bool MA, bool MB, bool PIN, bool BUF>
-void launch_vb(const F32GemmArgs& a, dim3 grid, hipStream_t s) {
-  if (a.vec_a && a.vec_b) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, true, true, PIN, BUF>), grid, dim3(256), 0, s, a);
-  else if (a.vec_a) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, true, false, PIN, BUF>), grid, dim3(256), 0, s, a);
-  else if (a.vec_b) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, false, true, PIN, BUF>), grid, dim3(256), 0, s, a);
+void launch_vb(const F32Selected& k, const F32GemmArgs& a, dim3 grid, hipStream_t s) {
+  if (k.va && k.vb) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, true, true, PIN, BUF>), grid, dim3(256), 0, s, a);
+  else if (k.va) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, true, false, PIN, BUF>), grid, dim3(256), 0, s, a);
+  else if (k.vb) hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, false, true, PIN, BUF>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((k_gemm_f32<MODE, MA, MB, false, false, PIN, BUF>), grid, dim3(256), 0, s, a);
 }
 
-// buffer-resource operand loads when both operands (and their masks) fit 32-bit byte offsets
-// (TDL_F32_BUF=0 keeps the 64-bit address form everywhere: A/B hook)
-bool f32_buf_ok(const F32GemmArgs& a) {
-  static const bool on = [] {
-    const char* e = std::getenv("TDL_F32_BUF");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  return on && a.na > 0 && a.nb > 0 && a.na < (int64_t(1) << 29) && a.nb < (int64_t(1) << 29);
-}
-
 template <int MODE, bool MA, bool MB, bool PIN = false>
-void launch_v(const F32GemmArgs& a, dim3 grid, hipStream_t s) {
-  if (f32_buf_ok(a) && !PIN) launch_vb<MODE, MA, MB, PIN, true>(a, grid, s);
-  else launch_vb<MODE, MA, MB, PIN, false>(a, grid, s);
+void launch_v(const F32Selected& k, const F32GemmArgs& a, dim3 grid, hipStream_t s) {
+  if (k.buf) {
+    launch_vb<MODE, MA, MB, PIN, true>(k, a, grid, s);
+    return;
+  }
+  launch_vb<MODE, MA, MB, PIN, false>(k, a, grid, s);
 }
 
 }  // namespace
 
-void f32_reduce16(bool on) { g_reduce16 = on; }
+namespace {
+bool swap_hook(bool& hook, bool on) {
+  const bool was = hook;
+  hook = on;
+  return was;
+}
+}  // namespace
+bool f32_reduce16(bool on) { return swap_hook(g_reduce16, on); }
+bool f32_buf(bool on) { return swap_hook(g_buf, on); }
+bool f32_reduce_narrow(bool on) { return swap_hook(g_reduce_narrow, on); }
+bool f32_pool_hoist(bool on) { return swap_hook(g_pool_hoist, on); }
 
-void f32_gemm_launch(int mode, const F32GemmArgs& a, hipStream_t s) {
-  if (a.M <= 0 || a.N <= 0) return;
+std::string F32Selected::main_name() const {
+  std::string n = kModeNames[mode];
+  auto flag = [&](const char* f, bool v) { n += std::string("_") + f + (v ? "1" : "0"); };
+  if (mode == kF32Gemm || mode == kF32ConvDgrad || mode == kF32ConvWgrad) flag("ma", ma);
+  if (mode == kF32Gemm) flag("mb", mb);
+  if (mode != kF32ConvWgrad) flag("va", va);
+  flag("vb", vb);
+  if (mode == kF32ConvDgrad || mode == kF32ConvWgrad) flag("pin", pin);
+  flag("buf", buf);
+  return n;
+}
+
+const char* F32Selected::reduce_name() const { return kReduceNames[reduce]; }
+
+F32Selected f32_gemm_selected(int mode, const F32GemmArgs& a) {
+  F32Selected k;
+  k.mode = mode < kF32Gemm || mode > kF32ConvWgrad ? (int)kF32ConvWgrad : mode;
+  k.splits = a.splits;
+  k.kchunk = a.kchunk;
+  const bool grad = k.mode == kF32ConvDgrad || k.mode == kF32ConvWgrad;
+  k.pin = grad && a.pin_arg != nullptr;
+  k.ma = k.pin || (k.mode != kF32ConvFwd && a.amask != nullptr);  // (pooled gradient: amask = the maximum)
+  k.mb = k.mode == kF32Gemm && a.bmask != nullptr;
+  k.va = k.mode != kF32ConvWgrad && a.vec_a != 0;
+  k.vb = a.vec_b != 0;
+  k.buf = !k.pin && f32_buf_ok(a);
+  const int64_t mn = (int64_t)a.M * a.N;
+  if (a.splits <= 1) {
+    k.reduce = kF32ReduceNone;
+  } else if (a.pool) {
+    if (g_pool_hoist && g_reduce_narrow && a.splits <= 4) k.reduce = kF32ReducePool4;  // (only the loads the slices
+    else if (g_pool_hoist && g_reduce_narrow && a.splits <= 8) k.reduce = kF32ReducePool8;  // need: same 16-term sums)
+    else if (g_pool_hoist) k.reduce = kF32ReducePool16;
+    else k.reduce = kF32ReducePoolRows;
+  } else if (a.splits >= 16) {
+    if (mn >= 512 * 16 && g_reduce16) k.reduce = mn % 4 == 0 ? kF32ReduceWave16V4 : kF32ReduceWave16S;  // >= 512 waves of 16
+    else if (mn >= 64 * 4 && g_reduce16) k.reduce = mn % 4 == 0 ? kF32ReduceWave4V4 : kF32ReduceWave4S;  // >= 64 waves of 4
+    else k.reduce = kF32ReduceWave;  // one wave per output: every partial of an output in one load round
+  } else {
+    if (g_reduce_narrow && a.splits <= 4) k.reduce = kF32Reduce4;
+    else if (g_reduce_narrow && a.splits <= 8) k.reduce = kF32Reduce8;
+    else k.reduce = kF32Reduce16;
+  }
+  return k;
+}
+
+std::vector<std::string> f32_kernel_names() {
+  std::vector<std::string> out;
+  for (int mode = kF32Gemm; mode <= kF32ConvWgrad; ++mode)
+    for (int bits = 0; bits < 64; ++bits) {
+      F32Selected k;
+      k.mode = mode;
+      k.ma = bits & 1, k.mb = bits & 2, k.va = bits & 4, k.vb = bits & 8, k.pin = bits & 16, k.buf = bits & 32;
+      // the combinations f32_gemm_selected can form: masks per mode, no VA weight gradient, the pooled
+      // gradient always masked and never through buffer resources
+      if (k.mb && mode != kF32Gemm) continue;
+      if (k.ma && mode == kF32ConvFwd) continue;
+      if (k.va && mode == kF32ConvWgrad) continue;
+      if (k.pin && (mode == kF32Gemm || mode == kF32ConvFwd || !k.ma || k.buf)) continue;
+      out.push_back(k.main_name());
+    }
+  for (int r = 0; r < kF32ReduceCount; ++r) out.push_back(kReduceNames[r]);
+  return out;
+}
+
+F32Selected f32_gemm_launch(int mode, const F32GemmArgs& a, hipStream_t s) {
+  const F32Selected k = f32_gemm_selected(mode, a);
+  if (a.M <= 0 || a.N <= 0) return k;
   const dim3 grid((a.M + kF32Tile - 1) / kF32Tile, (a.N + kF32Tile - 1) / kF32Tile, a.splits);
-  const bool ma = a.amask != nullptr, mb = a.bmask != nullptr;
-  switch (mode) {
+  switch (k.mode) {
     case kF32Gemm:
-      if (ma && mb) launch_v<kF32Gemm, true, true>(a, grid, s);
-      else if (ma) launch_v<kF32Gemm, true, false>(a, grid, s);
-      else if (mb) launch_v<kF32Gemm, false, true>(a, grid, s);
-      else launch_v<kF32Gemm, false, false>(a, grid, s);
+      if (k.ma && k.mb) launch_v<kF32Gemm, true, true>(k, a, grid, s);
+      else if (k.ma) launch_v<kF32Gemm, true, false>(k, a, grid, s);
+      else if (k.mb) launch_v<kF32Gemm, false, true>(k, a, grid, s);
+      else launch_v<kF32Gemm, false, false>(k, a, grid, s);
       break;
-    case kF32ConvFwd: launch_v<kF32ConvFwd, false, false>(a, grid, s); break;
+    case kF32ConvFwd: launch_v<kF32ConvFwd, false, false>(k, a, grid, s); break;
     case kF32ConvDgrad:
-      if (a.pin_arg != nullptr) launch_v<kF32ConvDgrad, true, false, true>(a, grid, s);  // (amask = the maximum)
-      else if (ma) launch_v<kF32ConvDgrad, true, false>(a, grid, s);
-      else launch_v<kF32ConvDgrad, false, false>(a, grid, s);
+      if (k.pin) launch_v<kF32ConvDgrad, true, false, true>(k, a, grid, s);
+      else if (k.ma) launch_v<kF32ConvDgrad, true, false>(k, a, grid, s);
+      else launch_v<kF32ConvDgrad, false, false>(k, a, grid, s);
       break;
     default:
-      if (a.pin_arg != nullptr) launch_v<kF32ConvWgrad, true, false, true>(a, grid, s);
-      else if (ma) launch_v<kF32ConvWgrad, true, false>(a, grid, s);
-      else launch_v<kF32ConvWgrad, false, false>(a, grid, s);
+      if (k.pin) launch_v<kF32ConvWgrad, true, false, true>(k, a, grid, s);
+      else if (k.ma) launch_v<kF32ConvWgrad, true, false>(k, a, grid, s);
+      else launch_v<kF32ConvWgrad, false, false>(k, a, grid, s);
       break;
   }
-  if (a.splits > 1 && a.pool) {
-    const int64_t wins = (int64_t)(a.M >> 2) * a.N;
-    static const bool hoist = [] {  // TDL_F32_POOLRED_HOIST=0: row by row (A/B hook)
-      const char* e = std::getenv("TDL_F32_POOLRED_HOIST");
-      return e == nullptr || std::atoi(e) != 0;
-    }();
-    const bool narrow = reduce_narrow();
-    if (hoist && narrow && a.splits <= 4)  // (only the loads the slices need: the 16-term sums unchanged)
-      hipLaunchKernelGGL((k_gemm_f32_reduce_pool<true, 4>), dim3((unsigned)((wins + 255) / 256)), dim3(256), 0, s, a);
-    else if (hoist && narrow && a.splits <= 8)
-      hipLaunchKernelGGL((k_gemm_f32_reduce_pool<true, 8>), dim3((unsigned)((wins + 255) / 256)), dim3(256), 0, s, a);
-    else if (hoist)
-      hipLaunchKernelGGL(k_gemm_f32_reduce_pool<true>, dim3((unsigned)((wins + 255) / 256)), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL(k_gemm_f32_reduce_pool<false>, dim3((unsigned)((wins + 255) / 256)), dim3(256), 0, s, a);
-  } else if (a.splits > 1) {
-    const int64_t mn = (int64_t)a.M * a.N;
-    if (a.splits >= 16 && mn >= 512 * 16 && reduce16_on()) {  // >= 512 waves of 16 outputs
-      const dim3 gr((unsigned)((mn + 63) / 64));
-      if (mn % 4 == 0)
-        hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<16, true>), gr, dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<16, false>), gr, dim3(256), 0, s, a);
-    } else if (a.splits >= 16 && mn >= 64 * 4 && reduce16_on()) {  // >= 64 waves of 4 outputs
-      const dim3 gr((unsigned)((mn + 15) / 16));
-      if (mn % 4 == 0)
-        hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<4, true>), gr, dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<4, false>), gr, dim3(256), 0, s, a);
-    } else if (a.splits >= 16)  // one wave per output: every partial of an output in one load round
-      hipLaunchKernelGGL(k_gemm_f32_reduce_wave, dim3((unsigned)((mn + 3) / 4)), dim3(256), 0, s, a);
-    else {
-      const bool narrow = reduce_narrow();
-      const dim3 gr((unsigned)((mn + 255) / 256));
-      if (narrow && a.splits <= 4)
-        hipLaunchKernelGGL(k_gemm_f32_reduce<4>, gr, dim3(256), 0, s, a);
-      else if (narrow && a.splits <= 8)
-        hipLaunchKernelGGL(k_gemm_f32_reduce<8>, gr, dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL(k_gemm_f32_reduce<16>, gr, dim3(256), 0, s, a);
-    }
+  const int64_t mn = (int64_t)a.M * a.N;
+  const int64_t wins = (int64_t)(a.M >> 2) * a.N;  // (pooled reduces: one thread per window and column)
+  const dim3 b(256);
+  switch (k.reduce) {
+    case kF32ReduceNone: break;
+    case kF32ReducePool4:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_pool<true, 4>), dim3((unsigned)((wins + 255) / 256)), b, 0, s, a);
+      break;
+    case kF32ReducePool8:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_pool<true, 8>), dim3((unsigned)((wins + 255) / 256)), b, 0, s, a);
+      break;
+    case kF32ReducePool16:
+      hipLaunchKernelGGL(k_gemm_f32_reduce_pool<true>, dim3((unsigned)((wins + 255) / 256)), b, 0, s, a);
+      break;
+    case kF32ReducePoolRows:
+      hipLaunchKernelGGL(k_gemm_f32_reduce_pool<false>, dim3((unsigned)((wins + 255) / 256)), b, 0, s, a);
+      break;
+    case kF32ReduceWave16V4:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<16, true>), dim3((unsigned)((mn + 63) / 64)), b, 0, s, a);
+      break;
+    case kF32ReduceWave16S:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<16, false>), dim3((unsigned)((mn + 63) / 64)), b, 0, s, a);
+      break;
+    case kF32ReduceWave4V4:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<4, true>), dim3((unsigned)((mn + 15) / 16)), b, 0, s, a);
+      break;
+    case kF32ReduceWave4S:
+      hipLaunchKernelGGL((k_gemm_f32_reduce_wave16<4, false>), dim3((unsigned)((mn + 15) / 16)), b, 0, s, a);
+      break;
+    case kF32ReduceWave:
+      hipLaunchKernelGGL(k_gemm_f32_reduce_wave, dim3((unsigned)((mn + 3) / 4)), b, 0, s, a);
+      break;
+    case kF32Reduce4:
+      hipLaunchKernelGGL(k_gemm_f32_reduce<4>, dim3((unsigned)((mn + 255) / 256)), b, 0, s, a);
+      break;
+    case kF32Reduce8:
+      hipLaunchKernelGGL(k_gemm_f32_reduce<8>, dim3((unsigned)((mn + 255) / 256)), b, 0, s, a);
+      break;
+    default:
+      hipLaunchKernelGGL(k_gemm_f32_reduce<16>, dim3((unsigned)((mn + 255) / 256)), b, 0, s, a);
+      break;
   }
+  return k;
 }
 
 }  // namespace tdl

@@ -933,21 +933,41 @@ void f32_check(const at::Tensor& t, const char* what) {
 }
 bool al16(const at::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
 
-void f32_run(int mode, tdl::F32GemmArgs& a, const at::TensorOptions& o) {
-  TORCH_CHECK(a.Kred > 0, "f32 gemm: empty reduction");
-  // TDL_F32_SPLIT="kmin,cap" (A/B of the split plan; default 64,1024)
+// TDL_F32_SPLIT="kmin,cap" (A/B of the split plan; default 64,1024)
+const std::pair<int, int>& f32_split_plan() {
   static const std::pair<int, int> plan = [] {
     int kmin = 64, cap = 1024;
     if (const char* e = std::getenv("TDL_F32_SPLIT")) std::sscanf(e, "%d,%d", &kmin, &cap);
     return std::make_pair(kmin < 16 ? 16 : kmin, cap < 1 ? 1 : cap);
   }();
+  return plan;
+}
+
+tdl::F32Selected g_f32_last;  // what the most recent f32 launch of this process took (f32_last_selected)
+
+void f32_run(int mode, tdl::F32GemmArgs& a, const at::TensorOptions& o) {
+  TORCH_CHECK(a.Kred > 0, "f32 gemm: empty reduction");
+  const auto& plan = f32_split_plan();
   tdl::f32_gemm_plan(a, plan.first, plan.second);
   at::Tensor ws;
   if (a.splits > 1) {
     ws = at::empty({(int64_t)a.splits * a.M * a.N}, o);
     a.ws = ws.data_ptr<float>();
   }
-  tdl::f32_gemm_launch(mode, a, cur_stream());
+  g_f32_last = tdl::f32_gemm_launch(mode, a, cur_stream());
+}
+
+// (splits, kchunk, unfused_splits) of an M x N x Kred problem (pool: the pooled conv, whose plan is the
+// unfused conv's over plan_m rows unless that has 16 or more slices); no device needed
+std::tuple<int64_t, int64_t, int64_t> f32_plan(int64_t M, int64_t N, int64_t Kred, bool pool, int64_t plan_m) {
+  TORCH_CHECK(M > 0 && N > 0 && Kred > 0, "f32_plan: positive sizes");
+  const auto& plan = f32_split_plan();
+  tdl::F32GemmArgs a{}, u{};
+  a.M = (int)M, a.N = (int)N, a.Kred = (int)Kred, a.pool = pool ? 1 : 0, a.plan_m = (int)plan_m;
+  u.M = (int)(plan_m > 0 ? plan_m : M), u.N = (int)N, u.Kred = (int)Kred;
+  tdl::f32_gemm_plan(a, plan.first, plan.second);
+  tdl::f32_gemm_plan(u, plan.first, plan.second);
+  return std::make_tuple((int64_t)a.splits, (int64_t)a.kchunk, (int64_t)u.splits);
 }
 
 const float* f32_bias(const c10::optional<at::Tensor>& bias, int64_t n) {
@@ -1356,7 +1376,21 @@ void register_ops(pybind11::module& m) {
         "conv main loop A/B hook: 1 v1 register staged, 2 default selection, 3 LDS-DMA ring, 4/5 dma1 at 4/3 waves "
         "per SIMD on 16x16x32 MFMAs, 6 dma1 on 32x32x16 MFMAs everywhere");
   m.def("f32_reduce16", &tdl::f32_reduce16,
-        "f32 split-K reduce A/B hook: 16 outputs per wave over many slices (True, default) or one output per wave");
+        "f32 split-K reduce A/B hook: 16 outputs per wave over many slices (True, default) or one output per wave; returns the previous setting");
+  m.def("f32_buf", &tdl::f32_buf,
+        "f32 operand loader A/B hook: buffer resources where the operands fit (True, default) or 64-bit addresses; returns the previous setting");
+  m.def("f32_reduce_narrow", &tdl::f32_reduce_narrow,
+        "f32 few-slice reduce A/B hook: only the loads 4 / 8 slices need (True, default) or always 16; returns the previous setting");
+  m.def("f32_pool_hoist", &tdl::f32_pool_hoist,
+        "f32 pooled reduce A/B hook: a window's partial sums loaded before any store (True, default) or row by row; returns the previous setting");
+  m.def("f32_last_selected", [] {
+    return std::make_tuple(g_f32_last.main_name(), std::string(g_f32_last.reduce_name()), g_f32_last.splits,
+                           g_f32_last.kchunk);
+  }, "(main kernel, reduce kernel, splits, kchunk) of the most recent f32 GEMM / conv launch of this process");
+  m.def("f32_kernel_names", &tdl::f32_kernel_names, "every main and reduce kernel name f32_last_selected can return");
+  m.def("f32_plan", &f32_plan, "(splits, kchunk, unfused_splits) of the f32 split plan; no GPU needed",
+        pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("Kred"), pybind11::arg("pool") = false,
+        pybind11::arg("plan_m") = 0);
   m.def("conv_force_halo", &tdl::conv_force_halo, "halo (input-reuse) main loop for stride-1 multi-tap convs: 1 on, 0 off");
   m.def("conv_force_mfma", &tdl::conv_force_mfma, "dma1 MFMA form: 32 (32x32x16, default) or 16 (16x16x32)");
   m.def("conv_wgrad3x3_set_rows", &tdl::conv_wgrad3x3_set_rows, "3x3 row-kernel wgrad: output rows per slice (0 = auto)");

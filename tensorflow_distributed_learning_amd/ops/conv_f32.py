@@ -124,7 +124,11 @@ def _conv_backward(ctx, x, w, y, dy, pin=None, unpool=None):
 class _ConvPoolF32(torch.autograd.Function):
     """conv (+ bias, + ReLU) followed by a 2x2 / stride-2 'valid' max pool: ONE forward launch (the pool in
     the GEMM epilogue, conv_f32_fwd_pool); the backward is the pool's (maxpool_bwd over the epilogue's
-    argmax) and then the conv's, exactly as the unfused pair."""
+    argmax) and then the conv's, exactly as the unfused pair.  The forward takes the unfused conv's
+    split-K plan and is bit-identical to ``max_pool(conv2d(...))`` wherever that plan has fewer than 16
+    slices (``hip().f32_plan(M, K, R*S*C, True, N*OH*OW)[2] < 16``); with 16 or more -- a long reduction
+    over few pixels, e.g. 1x10x10x128 into 64 channels, 3x3 -- it reduces in ONE slice instead and agrees
+    with the unfused pair to f32 rounding only."""
 
     @staticmethod
     def forward(ctx, x, w, b, stride, pads, dil, grad_out, anchor=None, act=0, gb_out=None):
@@ -173,7 +177,8 @@ def conv_pool_supported(x: torch.Tensor, oh: int, ow: int, k: int) -> bool:
 def conv2d_pool(x, w_hwio, bias=None, stride=(1, 1), pads=(0, 0, 0, 0), dil=(1, 1), grad_out=None, anchor=None,
                 act=0, gb_out=None):
     """``max_pool_2x2(act(conv(x, w) + bias))`` with the pool fused into the convolution's launch (see
-    :func:`conv2d` for the arguments)."""
+    :func:`conv2d` for the arguments; :class:`_ConvPoolF32` for when it equals the unfused pair bit for
+    bit).  A NaN pre-activation becomes 0 under ``act=1`` and never wins a window without it."""
     return _ConvPoolF32.apply(x, w_hwio, bias, tuple(int(s) for s in stride), tuple(int(p) for p in pads),
                               tuple(int(d) for d in dil), grad_out, anchor, int(act), gb_out)
 

@@ -1,11 +1,12 @@
 """f64 references of the bf16 implicit-GEMM convolution family (csrc/kernels/conv.hip, conv_wgrad.hip,
-wgrad3x3.hip, stem.hip), shared by test_conv_refs_cpu.py, test_conv_edges_gpu.py,
-test_conv_wgrad_edges_gpu.py and test_stem_edges_gpu.py.  numpy only; nothing here touches a GPU.
+wgrad3x3.hip, stem.hip) and of the generic f32 GEMM / convolution (gemm_f32.hip) with its fusions, shared
+by test_conv_refs_cpu.py, test_conv_edges_gpu.py, test_conv_wgrad_edges_gpu.py, test_stem_edges_gpu.py,
+test_gemm_f32_edges_gpu.py and test_conv_f32_edges_gpu.py.  numpy only; nothing here touches a GPU.
 
 Tensors are NHWC; weights come in the kernels' own layouts (OHWI forward, HWIO gradients).  Every
 convolution is a loop over filter taps with one einsum per tap, so the indexing is the definition:
-output pixel (oh, ow) of tap (kh, kw) reads input pixel (oh*SH - PT + kh, ow*SW - PL + kw) when that lies
-inside the image.  Bottom / right padding is implied by (OH, OW); rows and columns no output reaches are
+output pixel (oh, ow) of tap (kh, kw) reads input pixel (oh*SH - PT + kh*DH, ow*SW - PL + kw*DW) when that
+lies inside the image.  Bottom / right padding is implied by (OH, OW); rows and columns no output reaches are
 ignored.  Each convolution also returns sum |a||b| per output, for the error bound of the random-data
 tests and for the exactness precondition of the integer-data tests.
 
@@ -15,20 +16,20 @@ sums from the stored bf16 values.
 """
 import numpy as np
 
-from kernel_refs import bf16_bits_to_f64, bf16_rne, ulp_bf16
+from kernel_refs import _relu_fmaxf, bf16_bits_to_f64, bf16_rne, maxpool_fwd_ref, ulp_bf16
 
 EXACT_LIMIT = 2.0 ** 24  # integers below it are exact in f32, and so is every f32 sum of them in any order
 
 
-def _taps(H, OH, SH, PT, kh):
-    """(output rows, input rows) of the outputs whose tap kh lies inside an image of H rows."""
+def _taps(H, OH, SH, PT, kh, D=1):
+    """(output rows, input rows) of the outputs whose tap kh (dilation D) lies inside an image of H rows."""
     o = np.arange(OH)
-    i = o * SH - PT + kh
+    i = o * SH - PT + kh * D
     ok = (i >= 0) & (i < H)
     return o[ok], i[ok]
 
 
-def conv_fwd_ref(x, w_ohwi, oh, ow, sh=1, sw=1, pt=0, pl=0):
+def conv_fwd_ref(x, w_ohwi, oh, ow, sh=1, sw=1, pt=0, pl=0, *, dh=1, dw=1):
     """y [N,OH,OW,K] = conv(x [N,H,W,C], w [K,KH,KW,C]) in f64, and sum |x||w| per output."""
     x, w = np.asarray(x, np.float64), np.asarray(w_ohwi, np.float64)
     N, H, W, C = x.shape
@@ -37,9 +38,9 @@ def conv_fwd_ref(x, w_ohwi, oh, ow, sh=1, sw=1, pt=0, pl=0):
     ab = np.zeros((N, oh, ow, K))
     with np.errstate(invalid="ignore", over="ignore"):
         for kh in range(KH):
-            o_h, i_h = _taps(H, oh, sh, pt, kh)
+            o_h, i_h = _taps(H, oh, sh, pt, kh, dh)
             for kw in range(KW):
-                o_w, i_w = _taps(W, ow, sw, pl, kw)
+                o_w, i_w = _taps(W, ow, sw, pl, kw, dw)
                 if o_h.size == 0 or o_w.size == 0:
                     continue
                 xs = x[:, i_h][:, :, i_w]
@@ -48,7 +49,7 @@ def conv_fwd_ref(x, w_ohwi, oh, ow, sh=1, sw=1, pt=0, pl=0):
     return y, ab
 
 
-def conv_dgrad_ref(dy, w_hwio, h, w, sh=1, sw=1, pt=0, pl=0):
+def conv_dgrad_ref(dy, w_hwio, h, w, sh=1, sw=1, pt=0, pl=0, *, dh=1, dw=1):
     """dx [N,H,W,C] of a conv with output gradient dy [N,OH,OW,K] and weights [KH,KW,C,K] in f64: every
     output pixel's dy . w[kh, kw]^T added to the input pixel its tap (kh, kw) read.  And sum |dy||w|."""
     dy, wt = np.asarray(dy, np.float64), np.asarray(w_hwio, np.float64)
@@ -58,9 +59,9 @@ def conv_dgrad_ref(dy, w_hwio, h, w, sh=1, sw=1, pt=0, pl=0):
     ab = np.zeros((N, h, w, C))
     with np.errstate(invalid="ignore", over="ignore"):
         for kh in range(KH):
-            o_h, i_h = _taps(h, OH, sh, pt, kh)
+            o_h, i_h = _taps(h, OH, sh, pt, kh, dh)
             for kw in range(KW):
-                o_w, i_w = _taps(w, OW, sw, pl, kw)
+                o_w, i_w = _taps(w, OW, sw, pl, kw, dw)
                 if o_h.size == 0 or o_w.size == 0:
                     continue
                 ds = dy[:, o_h][:, :, o_w]  # (for one tap every output pixel reads a different input pixel)
@@ -75,24 +76,25 @@ def conv_dgrad_s2_ref(dy, w_hwio, h, w):
     return conv_dgrad_ref(dy, w_hwio, h, w, 2, 2, 0, 0)
 
 
-def conv_wgrad_ref(x, dy, kh_, kw_, sh=1, sw=1, pt=0, pl=0):
-    """dw [KH,KW,C,K] = sum over output pixels of x[tap pixel] (x) dy[pixel] in f64, and sum |x||dy|."""
+def conv_wgrad_ref(x, dy, kh_, kw_, sh=1, sw=1, pt=0, pl=0, *, dh=1, dw=1):
+    """dW [KH,KW,C,K] = sum over output pixels of x[tap pixel] (x) dy[pixel] in f64, and sum |x||dy|.
+    (dh, dw: the filter's dilation.)"""
     x, dy = np.asarray(x, np.float64), np.asarray(dy, np.float64)
     N, H, W, C = x.shape
     _, OH, OW, K = dy.shape
-    dw = np.zeros((kh_, kw_, C, K))
+    gw = np.zeros((kh_, kw_, C, K))
     ab = np.zeros((kh_, kw_, C, K))
     with np.errstate(invalid="ignore", over="ignore"):
         for kh in range(kh_):
-            o_h, i_h = _taps(H, OH, sh, pt, kh)
+            o_h, i_h = _taps(H, OH, sh, pt, kh, dh)
             for kw in range(kw_):
-                o_w, i_w = _taps(W, OW, sw, pl, kw)
+                o_w, i_w = _taps(W, OW, sw, pl, kw, dw)
                 if o_h.size == 0 or o_w.size == 0:
                     continue
                 xs, ds = x[:, i_h][:, :, i_w], dy[:, o_h][:, :, o_w]
-                dw[kh, kw] = np.einsum("nhwc,nhwk->ck", xs, ds)
+                gw[kh, kw] = np.einsum("nhwc,nhwk->ck", xs, ds)
                 ab[kh, kw] = np.einsum("nhwc,nhwk->ck", np.abs(xs), np.abs(ds))
-    return dw, ab
+    return gw, ab
 
 
 def assert_exact(absum, what="product sums"):
@@ -228,6 +230,65 @@ def dgrad_s2_epilogue_ref(acc, h, w, bm, res_bits=None, bn_y_bits=None, bn_x_bit
         if bn_x2_bits is not None:
             part2 = block_sums(bn_x2_bits)
     return v, part, part2
+
+
+# ------------------------------------------------------------------------------------- f32 fusions (gemm_f32.hip)
+def bias_act_ref(acc, bias=None, act=0, prior=None, fmaxf=True):
+    """Epilogue of the f32 kernels on the f64 result acc [..., N]: + bias[N], + prior (the accumulated
+    output), then the ReLU.  fmaxf: as the kernels take it (a NaN pre-activation gives 0); else max(v, 0),
+    where a NaN stays."""
+    v = np.asarray(acc, np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if bias is not None:
+            v = v + np.asarray(bias, np.float64)
+        if prior is not None:
+            v = v + np.asarray(prior, np.float64)
+        if act:
+            v = _relu_fmaxf(v) if fmaxf else np.maximum(v, 0.0)
+    return v
+
+
+def masked_ref(a, mask):
+    """The masked operand of the f32 kernels: a select on mask > 0 (not a product): an Inf or NaN element
+    under a mask <= 0 -- or under a NaN mask -- is an exact 0."""
+    if mask is None:
+        return np.asarray(a, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.asarray(mask) > 0, np.asarray(a, np.float64), 0.0)
+
+
+def bias_grad_ref(dy, mask=None):
+    """(db [K], sum |dy| [K]): the masked output gradient summed over every axis but the last."""
+    g = masked_ref(dy, mask)
+    g = g.reshape(-1, g.shape[-1])
+    with np.errstate(invalid="ignore", over="ignore"):
+        return g.sum(0), np.abs(g).sum(0)
+
+
+def conv_pool_fwd_ref(x, w_ohwi, bias, oh, ow, sh=1, sw=1, pt=0, pl=0, *, dh=1, dw=1, act=1):
+    """conv -> (+ bias) -> ReLU (fmaxf) -> 2x2 / stride-2 'valid' max pool: (y [N,OH,OW,K], maximum
+    [N,OH/2,OW/2,K], argmax uint8, sum |x||w| + |bias|).  The pool is kernel_refs.maxpool_fwd_ref: the first
+    maximum of the window in (dy, dx) order wins, a NaN never does, a window of NaNs gives -inf and 255."""
+    acc, ab = conv_fwd_ref(x, w_ohwi, oh, ow, sh, sw, pt, pl, dh=dh, dw=dw)
+    y = bias_act_ref(acc, bias, act)
+    if bias is not None:
+        ab = ab + np.abs(np.asarray(bias, np.float64))
+    ph, pw = oh // 2, ow // 2
+    mx, arg = maxpool_fwd_ref(y[:, :2 * ph, :2 * pw], 2, 2, 2, 2, 0, 0, 0, 0, False)
+    return y, mx, arg, ab
+
+
+def conv_pool_bwd_ref(dp, mx, arg, oh, ow):
+    """The conv-output gradient [N,OH,OW,K] the pooled-gradient loaders form from the pool's output gradient
+    dp [N,PH,PW,K]: dp at the window position its argmax names, where the pooled maximum is > 0 (the ReLU
+    mask); nothing where the argmax is 255; zero at pixels of an odd last row / column (in no window)."""
+    dp, mx, arg = np.asarray(dp, np.float64), np.asarray(mx), np.asarray(arg)
+    N, PH, PW, K = dp.shape
+    dy = np.zeros((N, oh, ow, K))
+    g = masked_ref(dp, mx)
+    for q in range(4):
+        dy[:, q // 2:2 * PH:2, q % 2:2 * PW:2] = np.where(arg == q, g, 0.0)
+    return dy
 
 
 # ------------------------------------------------------------------------------------- stem (stem.hip)

@@ -231,3 +231,176 @@ def test_stem_pack_ref_keeps_nan_payloads_and_copies_bf16_bits():
     assert list(xp[0, 0, 1:4, 1] >> 15) == [1, 1, 0]
     bits = np.array([0x7F81, 0xFFFF, 0x0001, 0x8000, 0x7F80], np.uint16).reshape(1, 1, 5, 1)  # signalling NaN, ...
     assert np.array_equal(CR.stem_pack_ref(bits, False, 1, 1, 1, (0, 0, 0, 0))[0, 0, :5, 0], bits.ravel())
+
+
+# ------------------------------------------------------------------------------------- f32 GEMM / conv references
+def _dilated_geoms():
+    # (N, H, W, C, K, KH, KW, SH, SW, DH, DW, pt, pb, pl, pr): stride, dilation and asymmetric pads together
+    rng = np.random.RandomState(23)
+    out = [(1, 7, 9, 2, 3, 3, 3, 2, 1, 2, 3, 1, 2, 3, 0), (2, 5, 5, 1, 2, 3, 2, 1, 2, 3, 2, 4, 2, 0, 1),
+           (1, 3, 4, 3, 2, 3, 3, 1, 1, 2, 2, 2, 2, 2, 2),  # the dilated filter (5x5) is larger than the image
+           (1, 6, 6, 2, 2, 1, 1, 3, 3, 2, 2, 0, 0, 0, 0)]  # 1x1: dilation has nothing to act on
+    while len(out) < 30:
+        N, H, W, C, K = rng.randint(1, 3), rng.randint(1, 10), rng.randint(1, 10), rng.randint(1, 4), rng.randint(1, 4)
+        KH, KW, SH, SW = rng.randint(1, 4), rng.randint(1, 4), rng.randint(1, 4), rng.randint(1, 4)
+        DH, DW = rng.randint(1, 4), rng.randint(1, 4)
+        pt, pb, pl, pr = (int(v) for v in rng.randint(0, 4, 4))
+        if H + pt + pb < (KH - 1) * DH + 1 or W + pl + pr < (KW - 1) * DW + 1:
+            continue
+        out.append((N, H, W, C, K, KH, KW, SH, SW, DH, DW, pt, pb, pl, pr))
+    return out
+
+
+@pytest.mark.parametrize("g", _dilated_geoms())
+def test_dilated_convolutions_match_torch_float64(g):
+    N, H, W, C, K, KH, KW, SH, SW, DH, DW, pt, pb, pl, pr = g
+    rng = np.random.RandomState(sum(g))
+    x, w = rng.randn(N, H, W, C), rng.randn(KH, KW, C, K)
+    xt = torch.tensor(x).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    wt = torch.tensor(w).permute(3, 2, 0, 1).contiguous().requires_grad_(True)
+    y = F.conv2d(F.pad(xt, (pl, pr, pt, pb)), wt, None, (SH, SW), 0, (DH, DW))
+    OH, OW = y.shape[2], y.shape[3]
+    got, ab = CR.conv_fwd_ref(x, w.transpose(3, 0, 1, 2), OH, OW, SH, SW, pt, pl, dh=DH, dw=DW)
+    np.testing.assert_allclose(got, y.detach().permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    want_ab = F.conv2d(F.pad(xt.detach().abs(), (pl, pr, pt, pb)), wt.detach().abs(), None, (SH, SW), 0, (DH, DW))
+    np.testing.assert_allclose(ab, want_ab.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    dy = np.random.RandomState(1).randn(N, OH, OW, K)
+    y.backward(torch.tensor(dy).permute(0, 3, 1, 2))
+    dx, _ = CR.conv_dgrad_ref(dy, w, H, W, SH, SW, pt, pl, dh=DH, dw=DW)
+    np.testing.assert_allclose(dx, xt.grad.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    gw, _ = CR.conv_wgrad_ref(x, dy, KH, KW, SH, SW, pt, pl, dh=DH, dw=DW)
+    np.testing.assert_allclose(gw, wt.grad.permute(2, 3, 1, 0).numpy(), rtol=1e-12, atol=1e-12)
+
+
+def test_dilation_defaults_leave_the_references_unchanged():
+    rng = np.random.RandomState(2)
+    x, w, dy = rng.randn(1, 6, 5, 2), rng.randn(3, 2, 2, 3), rng.randn(1, 3, 4, 3)
+    for a, b in zip(CR.conv_fwd_ref(x, w.transpose(3, 0, 1, 2), 3, 4, 2, 1, 1, 0),
+                    CR.conv_fwd_ref(x, w.transpose(3, 0, 1, 2), 3, 4, 2, 1, 1, 0, dh=1, dw=1)):
+        assert np.array_equal(a, b)
+    assert np.array_equal(CR.conv_dgrad_ref(dy, w, 6, 5, 2, 1, 1, 0)[0], CR.conv_dgrad_ref(dy, w, 6, 5, 2, 1, 1, 0, dh=1, dw=1)[0])
+    assert np.array_equal(CR.conv_wgrad_ref(x, dy, 3, 2, 2, 1, 1, 0)[0], CR.conv_wgrad_ref(x, dy, 3, 2, 2, 1, 1, 0, dh=1, dw=1)[0])
+
+
+def test_f32_fusion_references_on_hand_checked_values():
+    nan, inf = np.nan, np.inf
+    acc = np.array([[1.0, -2.0, nan], [-inf, 0.5, -1.0]])
+    b = np.array([1.0, 1.0, 1.0])
+    got = CR.bias_act_ref(acc, b, 1)
+    assert np.array_equal(got, [[2.0, 0.0, 0.0], [0.0, 1.5, 0.0]])  # fmaxf: the NaN pre-activation is 0
+    assert np.isnan(CR.bias_act_ref(acc, b, 1, fmaxf=False)[0, 2]) and np.isnan(CR.bias_act_ref(acc, b, 0)[0, 2])
+    assert np.array_equal(CR.bias_act_ref(acc[1:], None, 0, prior=np.array([[inf, 1.0, 1.0]]))[0, 1:], [1.5, 0.0])
+    assert np.isnan(CR.bias_act_ref(acc[1:], None, 0, prior=np.array([[inf, 1.0, 1.0]]))[0, 0])
+    # the mask is a select: Inf and NaN under mask <= 0 or a NaN mask are exact zeros, and -0 does not pass
+    a = np.array([inf, nan, 3.0, 4.0, -inf, 5.0])
+    m = np.array([0.0, -1.0, nan, 1e-30, -0.0, inf])
+    assert np.array_equal(CR.masked_ref(a, m), [0.0, 0.0, 0.0, 4.0, 0.0, 5.0])
+    assert CR.masked_ref(a, None) is not None and np.isnan(CR.masked_ref(a, None)[1])
+    db, ab = CR.bias_grad_ref(np.array([[[1.0, -2.0], [3.0, 4.0]], [[-5.0, 6.0], [inf, 8.0]]]),
+                              np.array([[[1.0, 1.0], [0.0, 1.0]], [[1.0, -1.0], [0.0, 1.0]]]))
+    assert list(db) == [-4.0, 10.0] and list(ab) == [6.0, 14.0]
+
+
+def test_pooled_forward_reference_ties_nans_and_odd_sizes():
+    # a 1x1 conv with weight 1 over a 3x5 image: y = relu(x); windows (0..1, 0..1) and (0..1, 2..3)
+    x = np.zeros((1, 3, 5, 1))
+    x[0, :2, :2, 0] = [[2.0, 7.0], [7.0, -1.0]]      # tie: the first maximum (position 1) wins
+    x[0, :2, 2:4, 0] = [[-3.0, np.nan], [-1.0, -2.0]]  # all <= 0 or NaN: relu gives zeros, position 0 wins
+    x[0, 2, :, 0] = 99.0  # the odd last row and column are in no window
+    w = np.ones((1, 1, 1, 1))
+    y, mx, arg, ab = CR.conv_pool_fwd_ref(x, w, None, 3, 5)
+    assert mx.shape == (1, 1, 2, 1) and list(mx.ravel()) == [7.0, 0.0] and list(arg.ravel()) == [1, 0]
+    assert y[0, 0, 3, 0] == 0.0 and y[0, 2, 0, 0] == 99.0
+    # without the ReLU the NaN stays in y, never wins, and a window of NaNs gives -inf and 255
+    x[0, :2, :2, 0] = np.nan
+    y, mx, arg, _ = CR.conv_pool_fwd_ref(x, w, None, 3, 5, act=0)
+    assert np.isnan(y[0, 0, 3, 0]) and list(mx.ravel()) == [-np.inf, -1.0] and list(arg.ravel()) == [255, 2]
+    # the backward: routed by argmax, masked by maximum > 0, nothing for 255 and nothing outside the windows
+    dy = CR.conv_pool_bwd_ref(np.array([5.0, 6.0, 7.0]).reshape(1, 1, 3, 1), np.array([1.0, 0.0, 2.0]).reshape(1, 1, 3, 1),
+                              np.array([3, 1, 255], np.uint8).reshape(1, 1, 3, 1), 3, 7)
+    want = np.zeros((1, 3, 7, 1))
+    want[0, 1, 1, 0] = 5.0
+    assert np.array_equal(dy, want)
+
+
+@pytest.mark.parametrize("g", [(2, 7, 8, 3, 4, 3, 3, 1, 1, 1, 1, 0, 0), (1, 9, 9, 2, 3, 3, 2, 2, 1, 1, 2, 1, 2),
+                               (2, 6, 6, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0), (1, 11, 7, 2, 2, 3, 3, 1, 2, 2, 1, 2, 1)])
+def test_pooled_references_match_autograd_of_pool_relu_conv(g):
+    N, H, W, C, K, KH, KW, SH, SW, DH, DW, pt, pl = g
+    rng = np.random.RandomState(sum(g))
+    x, w, b = rng.randn(N, H, W, C), rng.randn(KH, KW, C, K), rng.randn(K)  # (random f64: no ties)
+    xt = torch.tensor(x).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    wt = torch.tensor(w).permute(3, 2, 0, 1).contiguous().requires_grad_(True)
+    bt = torch.tensor(b).requires_grad_(True)
+    yt = F.conv2d(F.pad(xt, (pl, 0, pt, 0)), wt, bt, (SH, SW), 0, (DH, DW))
+    OH, OW = yt.shape[2], yt.shape[3]
+    pt_ = F.max_pool2d(torch.relu(yt), 2)
+    y, mx, arg, _ = CR.conv_pool_fwd_ref(x, w.transpose(3, 0, 1, 2), b, OH, OW, SH, SW, pt, pl, dh=DH, dw=DW)
+    np.testing.assert_allclose(y, torch.relu(yt).detach().permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(mx, pt_.detach().permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    assert arg.max() <= 3
+    dp = rng.randn(*mx.shape)
+    pt_.backward(torch.tensor(dp).permute(0, 3, 1, 2))
+    dy = CR.conv_pool_bwd_ref(dp, mx, arg, OH, OW)
+    dx, _ = CR.conv_dgrad_ref(dy, w, H, W, SH, SW, pt, pl, dh=DH, dw=DW)
+    gw, _ = CR.conv_wgrad_ref(x, dy, KH, KW, SH, SW, pt, pl, dh=DH, dw=DW)
+    np.testing.assert_allclose(dx, xt.grad.permute(0, 2, 3, 1).numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(gw, wt.grad.permute(2, 3, 1, 0).numpy(), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(CR.bias_grad_ref(dy)[0], bt.grad.numpy(), rtol=1e-12, atol=1e-12)
+
+
+def _f32_plan():
+    import glob
+    import os
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if not glob.glob(os.path.join(root, "tensorflow_distributed_learning_amd", "_C*.so")):
+        pytest.skip("extension not built (python build_native.py)")
+    from tensorflow_distributed_learning_amd.ops import hip
+
+    return hip().f32_plan
+
+
+def test_f32_split_plan_invariants(monkeypatch):
+    monkeypatch.delenv("TDL_F32_SPLIT", raising=False)
+    plan = _f32_plan()
+    Ms = [1, 4, 36, 63, 64, 65, 100, 1024, 4096, 16384, 32704, 32768, 32769, 100000]
+    Ns = [1, 8, 63, 64, 65, 289, 1024]
+    Ks = [1, 9, 15, 16, 17, 255, 256, 257, 288, 513, 1008, 1025, 1152, 4481, 16384, 65535, 65537, 70000, 1 << 20]
+    pooled_fallbacks = 0
+    for M in Ms:
+        for N in Ns:
+            for K in Ks:
+                s, c, u = plan(M, N, K)
+                assert c % 16 == 0 and (s - 1) * c < K <= s * c and 1 <= s <= 1024 and u == s, (M, N, K, s, c)
+                if K <= 256:
+                    assert s == 1, (M, N, K, s)
+                if M % 4 == 0:  # the pooled conv over M / 4 windows whose unfused conv has M .. rows
+                    for pm in (M, M + M // 8 + 1):
+                        sp, cp, up = plan(M, N, K, True, pm)
+                        s0, c0, _ = plan(pm, N, K)
+                        assert up == s0 and cp % 16 == 0 and (sp - 1) * cp < K <= sp * cp and sp < 16
+                        assert (sp == up and cp == c0) == (up < 16), (M, N, K, pm, sp, up)
+                        pooled_fallbacks += up >= 16
+                        if up >= 16:
+                            assert sp == 1
+    assert pooled_fallbacks > 50
+    # the shapes the GPU edge tests rely on
+    assert plan(5, 5, 257)[0] == 5 and plan(5, 5, 513)[0] == 9 and plan(5, 5, 1025)[0] == 17
+    assert plan(5, 5, 4481)[0] == 71 and plan(1, 1, 70000)[:2] == (875, 80) and plan(16384, 8, 260)[0] == 4
+    assert plan(36, 64, 9 * 112, True, 36) == (1, 1008, 16)
+
+
+def test_f32_hook_setters_return_the_value_they_replace():
+    _f32_plan()  # (skips when the extension is not built)
+    from tensorflow_distributed_learning_amd.ops import hip
+
+    C = hip()
+    for name in ("f32_buf", "f32_reduce_narrow", "f32_pool_hoist", "f32_reduce16"):
+        f = getattr(C, name)
+        start = f(False)
+        try:
+            assert f(True) is False and f(True) is True and f(False) is True
+        finally:
+            assert f(start) is False
+        assert f(start) is start

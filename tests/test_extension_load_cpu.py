@@ -18,7 +18,9 @@ def test_hip_extension_imports_with_every_entry_point():
     C = hip()
     for name in ("conv_fwd", "conv_fwd_stats", "conv_dgrad", "conv_dgrad_bn", "conv_dgrad_s2", "conv_wgrad",
                  "conv_wgrad_plans", "conv_force_impl", "conv_selected", "conv_kernel_names", "bn_forward_train", "bn_backward", "gemm_bf16", "MnistStep",
-                 "XgmiChannel", "stem_fwd", "maxpool_fwd"):
+                 "XgmiChannel", "stem_fwd", "maxpool_fwd", "gemm_f32", "conv_f32_fwd", "conv_f32_fwd_pool",
+                 "conv_f32_dgrad", "conv_f32_wgrad", "f32_last_selected", "f32_kernel_names", "f32_plan", "f32_reduce16",
+                 "f32_buf", "f32_reduce_narrow", "f32_pool_hoist"):
         assert hasattr(C, name), name
 
 
