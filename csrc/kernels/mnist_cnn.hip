@@ -744,11 +744,13 @@ constexpr int kLdsFwdFused = kLdsFwd + kDcF * kDcF * kDcFStride;
 constexpr int kP1Live = 12;
 constexpr int kConv1Tiles = kP1Live * kP1Live / 4;  // 36 conv1 row tiles of 4 pool windows
 // conv2 wgrad row tiles (first, count) per wave of the fused backward: waves w and w + 4 share a
-// SIMD; with tap skipping the dgrad MFMAs per SIMD are 192 / 168 / 144 / 144, and SIMDs 0 and 1
-// also run 6 of the dgrad's pool-1 / conv1-wgrad epilogues (3 pixel tiles per wave) where SIMDs 2
-// and 3 run 4.  SIMDs 0..3 take 3 / 4 / 5 / 6 of the 18 kernel-row tiles: 267 / 268 / 269 / 294
-// MFMAs per SIMD.  (4 / 4 / 5 / 5 evens the MFMAs out, 292 / 268 / 269 / 269, but SIMD 0 then ended
-// the kernel 0.2-0.6 us after the others: profiles/mnist_dead_border.txt.)  The bias row
+// SIMD; with tap skipping the dgrad MFMAs per SIMD are 192 / 168 / 144 / 144, SIMDs 0 and 1 carry
+// 6 of the dgrad's pool-1 / conv1-wgrad epilogues (3 pixel tiles per wave) where SIMDs 2 and 3
+// carry 4, and wave 0 starts its backward behind its own set-up (fused_bwd_pre; it ran the head
+// while the others prepared).  SIMDs 0..3 take 3 / 4 / 5 / 6 of the 18 kernel-row tiles: 267 / 268 /
+// 269 / 294 MFMAs per SIMD.  (4 / 4 / 5 / 5 evens the MFMAs out, 292 / 268 / 269 / 269, but was
+// slower both with the epilogues behind the MFMAs, profiles/mnist_dead_border.txt, and with them
+// between the MFMAs, +1.7 % per step: profiles/mnist_bwd_overlap.txt.)  The bias row
 // (db2 = the column sums of dC2 = the sums of the masked dP2 over the pool windows) is summed on
 // the VALU in the dP2 phase instead of a 19th MFMA tile against a unit vector.
 __constant__ int kFusedWgradTiles[8][2] = {{0, 2}, {3, 2}, {7, 3}, {12, 3}, {2, 1}, {5, 2}, {10, 2}, {15, 3}};
@@ -760,30 +762,91 @@ __device__ __forceinline__ void bwd_stamp(unsigned long long* buf, int k) {
     buf[(size_t)gridDim.x * 72 + (blockIdx.x * 8 + (threadIdx.x >> 6)) * 4 + k] = __builtin_amdgcn_s_memrealtime();
 }
 
+// diagnostics build (-DTDL_DIAG_DGRAD_STAMP): one more per-wave stamp, where the dgrad's MFMAs are
+// all issued and only epilogue work is left, behind the fused kernel's and KF-X's stamps:
+// buf[grid*104 + kFxBlocks*16 + workgroup*8 + wave] (scripts/stamps_mnist.py)
+__device__ __forceinline__ void dgrad_mfma_stamp(unsigned long long* buf) {
+#ifdef TDL_DIAG_DGRAD_STAMP
+  if (buf != nullptr && (threadIdx.x & 63) == 0)
+    buf[(size_t)gridDim.x * 104 + kFxBlocks * 16 + blockIdx.x * 8 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+
+// What a wave's share of the fused conv backward needs from the FORWARD's data only (LDS offsets
+// in floats, operands that do not depend on dH): computed by fused_bwd_pre while the wave waits for
+// its image's head, instead of after dH arrives.
+constexpr int kWgS = 3;  // k-steps per block of the conv2 wgrad's software pipeline
+struct FusedBwdPre {
+  // conv2 wgrad, row tiles t0 + u: the A (P1) offset of k-step 0, the B (dC2) offset, and the A
+  // operands of the pipeline's first block
+  int wga[3], wgb;
+  float wav[kWgS][3];
+  // conv2 dgrad, pixel tiles (wave & 3) + 4 u: the A (dC2) offset of cell (ih + 2, iw + 2), and the
+  // epilogue's operands of the lane's 4 pixels -- the ReLU mask source P1 and the offset in the
+  // image of the pool-1 argmax position's 3 x 3 patch
+  int dga[3], xo[3][4];
+  float p1v[3][4];
+};
+
+// the conv2 wgrad's k-step st covers positions p = 4 st + g = 10 q + r + g of the 10 x 10 grid; for
+// r = 8 lanes g >= 2 wrap to the next row: +3 P1 cells (and +5 dC cells)
+__device__ __forceinline__ int wg_wrap_a(int g) { return g >= 2 ? 3 * kP1Stride : 0; }
+
+__device__ __forceinline__ void fused_bwd_pre(FusedBwdPre& pre, const float* P1s, const uint8_t* a1s) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int i = lane & 15, g = lane >> 4;
+  const int t0 = kFusedWgradTiles[wave][0];
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int k = min(t0 + u, 17) * 16 + i;  // (a wave with fewer than 3 tiles: the last tile again, unused)
+    const int tap = k >> 5, ci = k & 31;
+    const int kh = tap / 3, kw = tap - kh * 3;
+    pre.wga[u] = (kh * 13 + kw + g) * kP1Stride + ci;
+  }
+  pre.wgb = (2 * kDcF + 2 + g) * kDcFStride + i;
+#pragma unroll
+  for (int j = 0; j < kWgS; ++j) {
+    const int q = (4 * j) / 10, r = (4 * j) % 10;
+#pragma unroll
+    for (int u = 0; u < 3; ++u) pre.wav[j][u] = P1s[pre.wga[u] + (q * 13 + r) * kP1Stride + (r == 8 ? wg_wrap_a(g) : 0)];
+  }
+  const int nt = wave >> 2, wt = wave & 3, ci = 16 * nt + i;
+#pragma unroll
+  for (int u = 0; u < 3; ++u) {
+    const int t = wt + 4 * u;  // (<= 11; waves with two tiles: a clamped third, unused)
+    const int Pc = min(t * 16 + i, 168);
+    const int ih = Pc / 13, iw = Pc - ih * 13;
+    pre.dga[u] = ((ih + 2) * kDcF + iw + 2) * kDcFStride + 4 * g;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int Pr = min(t * 16 + 4 * g + r, 168);
+      pre.p1v[u][r] = P1s[Pr * kP1Stride + ci];
+      const int q1 = a1s[Pr * 32 + ci];
+      const int ph = Pr / 13, pw = Pr - ph * 13;
+      pre.xo[u][r] = (2 * ph + (q1 >> 1)) * 28 + 2 * pw + (q1 & 1);
+    }
+  }
+}
+
 // N consecutive conv2 wgrad row tiles t0 .. t0+N-1 (kernel rows 16 t .. 16 t + 15) of the fused
 // backward, advanced together over the 25 k-steps; stores part2 rows of image bi.
 template <int N>
 __device__ __forceinline__ void fused_wgrad_tiles(const MnistArgs& a, int bi, int cq, int t0, const float* P1s,
-                                                  const float* dCs) {
+                                                  const float* dCs, const FusedBwdPre& pre) {
   const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
   const float* pa0[N];
 #pragma unroll
-  for (int u = 0; u < N; ++u) {
-    const int k = (t0 + u) * 16 + i;
-    const int tap = k >> 5, ci = k & 31;
-    const int kh = tap / 3, kw = tap - kh * 3;
-    pa0[u] = P1s + (kh * 13 + kw + g) * kP1Stride + ci;
-  }
-  // positions p = 10q + r + g; for r = 8 lanes g >= 2 wrap to the next row: +3 P1 cells, +5 dC cells
-  const int wrapA = g >= 2 ? 3 * kP1Stride : 0, wrapB = g >= 2 ? 5 * kDcFStride : 0;
-  const float* pb0 = dCs + (2 * kDcF + 2 + g) * kDcFStride + i;
+  for (int u = 0; u < N; ++u) pa0[u] = P1s + pre.wga[u];
+  const int wrapA = wg_wrap_a(g), wrapB = g >= 2 ? 5 * kDcFStride : 0;
+  const float* pb0 = dCs + pre.wgb;
   f4 acc[N];
 #pragma unroll
   for (int u = 0; u < N; ++u) acc[u] = zero4();
   // software pipeline over blocks of kS k-steps: the operands of block n + 1 are read while the
   // MFMAs of block n issue (sched barriers keep the compiler from sinking the reads back to their
-  // first use, which exposed the LDS latency before every MFMA); <= 12 reads in flight
-  constexpr int kS = 3, kBlocks = (25 + kS - 1) / kS;
+  // first use, which exposed the LDS latency before every MFMA); <= 12 reads in flight.  Block 0's
+  // P1 operands come with pre; only its dC2 operands are read here.
+  constexpr int kS = kWgS, kBlocks = (25 + kS - 1) / kS;
   float bv[2][kS], av[2][kS][N];
   auto load = [&](int buf, int blk) {
 #pragma unroll
@@ -794,7 +857,8 @@ __device__ __forceinline__ void fused_wgrad_tiles(const MnistArgs& a, int bi, in
       const bool strad = r == 8;
       bv[buf][j] = pb0[(q * kDcF + r) * kDcFStride + (strad ? wrapB : 0)];
 #pragma unroll
-      for (int u = 0; u < N; ++u) av[buf][j][u] = pa0[u][(q * 13 + r) * kP1Stride + (strad ? wrapA : 0)];
+      for (int u = 0; u < N; ++u)
+        av[buf][j][u] = blk == 0 ? pre.wav[j][u] : pa0[u][(q * 13 + r) * kP1Stride + (strad ? wrapA : 0)];
     }
   };
   load(0, 0);
@@ -835,23 +899,160 @@ __device__ __forceinline__ void lds_dgrad_w2(const float* w2d, f4 (&bwd)[9]) {
   for (int tap = 0; tap < 9; ++tap) bwd[tap] = ld4(w2d + (tap * 32 + 16 * nt + i) * 16 + 4 * g);
 }
 
+// kernel rows kh of the conv2 dgrad's pixel tile t (pixels 16 t .. 16 t + 15 of the 13 x 13 grid,
+// t <= 9) with 0 <= ih - kh <= 9 for some pixel row ih of the tile; the taps of the other rows read
+// only zeros of the dC2 grid and are not issued
+constexpr int dg_kh_lo(int t) { return (16 * t) / 13 > 9 ? (16 * t) / 13 - 9 : 0; }
+constexpr int dg_kh_hi(int t) { return (16 * t + 15) / 13 < 2 ? (16 * t + 15) / 13 : 2; }
+constexpr int dg_taps(int t) { return 3 * (dg_kh_hi(t) - dg_kh_lo(t) + 1); }
+// the pixel tiles 2 / 3 and 6 / 7 of waves wt = 2 / 3 issue all 9 taps: one instantiation for both
+static_assert(dg_taps(2) == 9 && dg_taps(3) == 9 && dg_taps(6) == 9 && dg_taps(7) == 9, "tile class 2");
+static_assert(dg_taps(0) == 6 && dg_taps(4) == 9 && dg_taps(8) == 9 && dg_taps(1) == 9 && dg_taps(5) == 9 &&
+              dg_taps(9) == 3, "tile classes 0 and 1");
+
+#define TDL_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
+
+// ---- conv2 dgrad of one wave of the fused backward + pool-1 / ReLU backward + conv1 wgrad, for its
+// pixel tiles wt + 4 u (WTC = min(wt, 2): the tiles' tap ranges are compile-time, so the whole
+// stream is one basic block).  The tiles run ONE AFTER ANOTHER, each over its taps in ascending order
+// on the accumulator pair (acc0: x.x, x.z; acc1: x.y, x.w), and the epilogue of tile u -- per pixel
+// row r the masked dP1 value v times the 3 x 3 image patch at the pool-1 argmax, 36 (ds_read_b32,
+// fmaf) pairs per lane -- is issued BETWEEN the MFMAs of tile u + 1 (one image tap = 4 pairs per
+// dgrad tap, 3 where tile 9 has only 3 taps), its image values read one tap ahead like the dC2
+// operands.  Run after all of a wave's MFMAs, the 2-3 epilogues per wave left the SIMD's MFMA pipe
+// idle for 0.8-1.1 us (profiles/mnist_bwd_overlap.txt); now only the last tile's 36 fmaf stay
+// behind the stream (its image values are read under its own MFMAs too).  dw[k] still accumulates
+// in (u ascending, r ascending) order: bit-identical sums. ----
+template <int WTC>
+__device__ __forceinline__ void fused_dgrad(const FusedBwdPre& pre, const float* dCs, const float* xs,
+                                            const f4 (&bwd)[9], float (&dw)[10], unsigned long long* stamps) {
+  constexpr int kT = WTC < 2 ? 3 : 2;
+  auto lda = [&](int u, int tap) {
+    const int kh = tap / 3, kw = tap - kh * 3;
+    return ld4(dCs + pre.dga[u] - (kh * kDcF + kw) * kDcFStride);
+  };
+  auto ldx = [&](int u, int k, int r) { return xs[pre.xo[u][r] + (k / 3) * 28 + k % 3]; };
+  f4 acc0 = zero4(), acc1 = zero4(), pacc0 = zero4(), pacc1 = zero4();
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  f4 av[2];
+  float ev[2][12];  // image values of the previous tile's epilogue: this step's / the next step's
+  float el[9][4];   // image values of the last tile's own epilogue
+  av[0] = lda(0, 3 * dg_kh_lo(WTC));
+  auto tile = [&](auto uc, auto sc) {
+    constexpr int u = decltype(uc)::value, t = WTC + 4 * u, up = u > 0 ? u - 1 : 0;
+    constexpr int s0 = decltype(sc)::value;  // steps (taps) issued before this tile: the double buffers' parity
+    constexpr int tap0 = 3 * dg_kh_lo(t), nA = dg_taps(t);
+    constexpr int cps = u > 0 ? 9 / nA : 0;      // image taps of tile u - 1's epilogue per step
+    constexpr int lps = u + 1 == kT ? 9 / nA : 0;  // last tile: image taps of its own epilogue read per step
+    static_assert((u == 0 || cps * nA == 9) && (u + 1 < kT || lps * nA == 9), "epilogue split over the taps");
+    acc0 = zero4();
+    acc1 = zero4();
+#pragma unroll
+    for (int j = 0; j < nA; ++j) {
+      const int p = (s0 + j) & 1;
+      // the next step's operands in flight while this step's MFMAs issue
+      if (j + 1 < nA) {
+        av[p ^ 1] = lda(u, tap0 + j + 1);
+#pragma unroll
+        for (int e = 0; e < 4 * cps; ++e) ev[p ^ 1][e] = ldx(up, (j + 1) * cps + (e >> 2), e & 3);
+      } else if constexpr (u + 1 < kT) {
+        constexpr int ncps = 9 / dg_taps(t + 4);
+        av[p ^ 1] = lda(u + 1, 3 * dg_kh_lo(t + 4));
+#pragma unroll
+        for (int e = 0; e < 4 * ncps; ++e) ev[p ^ 1][e] = ldx(u, e >> 2, e & 3);
+      }
+#pragma unroll
+      for (int e = 0; e < 4 * lps; ++e) el[j * lps + (e >> 2)][e & 3] = ldx(u, j * lps + (e >> 2), e & 3);
+      __builtin_amdgcn_sched_barrier(0);
+      const f4 x = av[p], bv = bwd[tap0 + j];
+      // pairs [first, first + n) of this step's share of tile u - 1's epilogue: image tap j cps + c, row r
+      auto fmas = [&](int first, int n) {
+#pragma unroll
+        for (int e = first; e < first + n; ++e) {
+          const int k = j * cps + (e >> 2);
+          dw[k] = fmaf(ev[p][e], v[e & 3], dw[k]);
+        }
+      };
+      if (u > 0 && j == 0) {
+        // tile u - 1's sums, once its last MFMAs have left the pipe behind two of this tile's
+        acc0 = mfma16x16x4(x.x, bv.x, acc0);
+        acc1 = mfma16x16x4(x.y, bv.y, acc1);
+        const f4 ac = pacc0 + pacc1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          v[r] = pre.p1v[up][r] > 0.f ? ac[r] : 0.f;
+          dw[9] += v[r];
+        }
+        acc0 = mfma16x16x4(x.z, bv.z, acc0);
+        fmas(0, 2 * cps);
+        acc1 = mfma16x16x4(x.w, bv.w, acc1);
+        fmas(2 * cps, 2 * cps);
+        TDL_SGB(0x8, 2);
+        TDL_SGB(0x2, 16);
+        TDL_SGB(0x8, 1);
+        TDL_SGB(0x2, 2 * cps);
+        TDL_SGB(0x8, 1);
+        TDL_SGB(0x2, 2 * cps);
+      } else {
+        acc0 = mfma16x16x4(x.x, bv.x, acc0);
+        fmas(0, cps);
+        acc1 = mfma16x16x4(x.y, bv.y, acc1);
+        fmas(cps, cps);
+        acc0 = mfma16x16x4(x.z, bv.z, acc0);
+        fmas(2 * cps, cps);
+        acc1 = mfma16x16x4(x.w, bv.w, acc1);
+        fmas(3 * cps, cps);
+        if constexpr (cps > 0) {
+#pragma unroll
+          for (int m = 0; m < 4; ++m) {
+            TDL_SGB(0x8, 1);
+            TDL_SGB(0x2, cps);
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    pacc0 = acc0;
+    pacc1 = acc1;
+  };
+  constexpr int n0 = dg_taps(WTC), n1 = dg_taps(WTC + 4);
+  tile(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+  tile(std::integral_constant<int, 1>{}, std::integral_constant<int, n0>{});
+  if constexpr (kT == 3) tile(std::integral_constant<int, 2>{}, std::integral_constant<int, n0 + n1>{});
+  dgrad_mfma_stamp(stamps);
+  // the last tile's epilogue, behind the stream
+  const f4 ac = pacc0 + pacc1;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float vl = pre.p1v[kT - 1][r] > 0.f ? ac[r] : 0.f;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dw[k] = fmaf(el[k][r], vl, dw[k]);
+    dw[9] += vl;
+  }
+}
+#undef TDL_SGB
+
 __device__ __forceinline__ void fused_conv_bwd(const MnistArgs& a, int bi, int cq, const float* dp2s,
                                                const uint8_t* a2s, const float* P1s, const uint8_t* a1s,
-                                               const float* xs, float* dCs, float* red, const f4 (&bwd)[9]) {
+                                               const float* xs, float* dCs, float* red, const f4 (&bwd)[9],
+                                               FusedBwdPre& pre) {
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const int i = lane & 15, g = lane >> 4;
   // (the dC2 grid dCs is complete: zeroed during conv2, the masked dP2 values scattered to their
   // pool-2 argmax cells by the dP2 phase, behind the caller's barrier)
   bwd_stamp(a.stamps, 0);
+  // (wave 0 ran the head while the others waited and prepared: its set-up comes now.  Ahead of its
+  // polls it delayed the head: +1.7 % per step, profiles/mnist_bwd_overlap.txt)
+  if (wave == 0) fused_bwd_pre(pre, P1s, a1s);
 
   // ---- conv2 wgrad: dW2[k = tap*32 + ci][16cq + co] over the 100 used positions.  k-step s
   // covers positions 4s + g of the 10 x 10 grid (see k_conv_bwd).  All of a wave's row tiles
   // advance together: one dC2 (B) read per k-step serves N MFMAs on N independent accumulators ----
   auto wgrad = [&]() {
     const int t0 = kFusedWgradTiles[wave][0], ntiles = kFusedWgradTiles[wave][1];
-    if (ntiles == 2) fused_wgrad_tiles<2>(a, bi, cq, t0, P1s, dCs);
-    else if (ntiles == 3) fused_wgrad_tiles<3>(a, bi, cq, t0, P1s, dCs);
-    else fused_wgrad_tiles<1>(a, bi, cq, t0, P1s, dCs);
+    if (ntiles == 2) fused_wgrad_tiles<2>(a, bi, cq, t0, P1s, dCs, pre);
+    else if (ntiles == 3) fused_wgrad_tiles<3>(a, bi, cq, t0, P1s, dCs, pre);
+    else fused_wgrad_tiles<1>(a, bi, cq, t0, P1s, dCs, pre);
   };
   // the wgrad and the dgrad of a wave are independent: with kMnistVariantStagger the younger half
   // (waves 4-7, each the SIMD partner of wave w - 4) runs them in the opposite order, so the two
@@ -863,91 +1064,16 @@ __device__ __forceinline__ void fused_conv_bwd(const MnistArgs& a, int bi, int c
   // ---- conv2 dgrad over this quarter's 16 output channels (a partial sum of dP1; everything after
   // it -- ReLU mask, pool-1 routing, conv1 wgrad -- is linear in dP1, so the four quarters'
   // conv1 weight gradients simply add up in the finalize reduction).  Waves 4nt .. 4nt+3 own input
-  // channels ci = 16nt + i and pixel tiles w, w + 4, w + 8 (16 pixels each), advanced together.
-  // Tile 10 (pixels 160..168, all in the dead row 12 of P1: no MFMA, an epilogue of exact zeros)
+  // channels ci = 16nt + i and pixel tiles w, w + 4, w + 8 (16 pixels each), one after another
+  // (fused_dgrad).  Tile 10 (pixels 160..168, all in the dead row 12 of P1: no MFMA, an epilogue of exact zeros)
   // and the empty tile 11 are not issued at all: waves 2, 3, 6, 7 run two tiles ----
   float dw[10];
 #pragma unroll
   for (int j = 0; j < 10; ++j) dw[j] = 0.f;
-  const int nt = wave >> 2, wt = wave & 3;
-  auto dgrad = [&](auto ktiles) {
-    constexpr int kT = decltype(ktiles)::value;
-    const int ci = 16 * nt + i;
-    f4 acc[kT][2];
-    int ih[kT], iw[kT], khlo[kT], khhi[kT];
-#pragma unroll
-    for (int u = 0; u < kT; ++u) {
-      const int t = wt + 4 * u;  // <= 9
-      const int Pc = min(t * 16 + i, 168);
-      ih[u] = Pc / 13;
-      iw[u] = Pc - ih[u] * 13;
-      const int ih_lo = min(t * 16, 168) / 13, ih_hi = min(t * 16 + 15, 168) / 13;
-      khlo[u] = t < 11 ? max(0, ih_lo - 9) : 3;  // kernel rows with 0 <= ih - kh <= 9 somewhere in the tile
-      khhi[u] = min(2, ih_hi);
-      acc[u][0] = zero4();
-      acc[u][1] = zero4();
-    }
-    // epilogue operands (ReLU mask source P1, pool-1 argmax) read ahead of the MFMAs
-    float p1v[kT][4];
-    unsigned q1v[kT][4];
-#pragma unroll
-    for (int u = 0; u < kT; ++u)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int Pr = min((wt + 4 * u) * 16 + 4 * g + r, 168);
-        p1v[u][r] = P1s[Pr * kP1Stride + ci];
-        q1v[u][r] = a1s[Pr * 32 + ci];
-      }
-    // taps software-pipelined: the dC2 reads of tap k + 1 are in flight while tap k's MFMAs issue
-    f4 av[2][kT];
-    auto load = [&](int buf, int tap) {
-      const int kh = tap / 3, kw = tap - kh * 3;
-#pragma unroll
-      for (int u = 0; u < kT; ++u)
-        av[buf][u] = ld4(dCs + ((ih[u] - kh + 2) * kDcF + (iw[u] - kw + 2)) * kDcFStride + 4 * g);
-    };
-    load(0, 0);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      if (tap + 1 < 9) load((tap + 1) & 1, tap + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      const int kh = tap / 3;
-      const f4 bv = bwd[tap];
-#pragma unroll
-      for (int u = 0; u < kT; ++u) {
-        if (kh < khlo[u] || kh > khhi[u]) continue;  // wave-uniform
-        const f4 x = av[tap & 1][u];
-        acc[u][0] = mfma16x16x4(x.x, bv.x, acc[u][0]);
-        acc[u][1] = mfma16x16x4(x.y, bv.y, acc[u][1]);
-        acc[u][0] = mfma16x16x4(x.z, bv.z, acc[u][0]);
-        acc[u][1] = mfma16x16x4(x.w, bv.w, acc[u][1]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int u = 0; u < kT; ++u) {
-      const int t = wt + 4 * u;
-      if (t >= 11) continue;
-      const f4 ac = acc[u][0] + acc[u][1];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int Pr = t * 16 + 4 * g + r;
-        if (Pr < 169) {
-          const float v = p1v[u][r] > 0.f ? ac[r] : 0.f;
-          const unsigned q1 = q1v[u][r];
-          const int ph = Pr / 13, pw = Pr - ph * 13;
-          const float* img = xs + (2 * ph + (q1 >> 1)) * 28 + 2 * pw + (q1 & 1);
-#pragma unroll
-          for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) dw[kh * 3 + kw] = fmaf(img[kh * 28 + kw], v, dw[kh * 3 + kw]);
-          dw[9] += v;
-        }
-      }
-    }
-  };
-  if (wt < 2) dgrad(std::integral_constant<int, 3>{});  // (wave-uniform)
-  else dgrad(std::integral_constant<int, 2>{});
+  const int wt = wave & 3;  // (wave-uniform)
+  if (wt == 0) fused_dgrad<0>(pre, dCs, xs, bwd, dw, a.stamps);
+  else if (wt == 1) fused_dgrad<1>(pre, dCs, xs, bwd, dw, a.stamps);
+  else fused_dgrad<2>(pre, dCs, xs, bwd, dw, a.stamps);
   if (swap) wgrad();
   bwd_stamp(a.stamps, 2);
 #pragma unroll
@@ -1326,6 +1452,11 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   if (!last) store_saved_fwd(a, bi, cq, P1s, a1s, p2s, a2s, tid, 512);
   else if (wave != 0) store_saved_fwd(a, bi, cq, P1s, a1s, p2s, a2s, tid - 64, 448);
   if (!a.dp2_fwd) return;  // dP2 by k_dense1_bwd
+  // the fused backward's set-up that reads only forward data (wgrad / dgrad LDS offsets, the wgrad's
+  // first P1 operands, the dgrad epilogue's ReLU masks and argmax patches): waves 1-7 have nothing to
+  // do until wave 0's head publishes dH (~3 us), so they run it here; wave 0 in fused_conv_bwd
+  FusedBwdPre pre;
+  if (a.fused_bwd && uwave != 0) fused_bwd_pre(pre, P1s, a1s);
   // ---- dP2 = (dH W3^T) * 1[P2 > 0] for this quarter's 400 features, from the W3 slice still in
   // registers (no K5 launch, no second read of W3), dH from this workgroup's own head (LDS) ----
   lds_barrier();
@@ -1372,7 +1503,7 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
       st4_sc1(rs, (((kP2Quads - 1) * 64 + 16 * cq + rg) * 4) * 4, f4{sb, 0.f, 0.f, 0.f});
     }
     lds_barrier();
-    fused_conv_bwd(a, bi, cq, p2s, a2s, P1s, a1s, xs, dCs, red, bwd);
+    fused_conv_bwd(a, bi, cq, p2s, a2s, P1s, a1s, xs, dCs, red, bwd, pre);
     return;
   }
   if (j < 25) {

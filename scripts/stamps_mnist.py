@@ -38,7 +38,10 @@ def main():
     for name, (k, waves, slots, grid) in KERNELS.items():
         if fused and name == "conv_bwd":
             continue
-        buf = torch.zeros(grid * 104, dtype=torch.int64, device=dev)
+        # fused kernel: grid * 104 words, then KF-X's (not launched here), then the diagnostics build's
+        # "dgrad MFMAs issued" stamp per wave (-DTDL_DIAG_DGRAD_STAMP; zeros in a normal build)
+        diag0 = grid * 104 + M.FINALIZE_BLOCKS * 16
+        buf = torch.zeros(diag0 + grid * 8, dtype=torch.int64, device=dev)
         st.forward_backward(0)
         st.finalize(True)
         st._impl.set_stamps(buf)
@@ -75,12 +78,21 @@ def main():
                       f"us (p10 {np.percentile(lat, 10):.2f}, p90 {np.percentile(lat, 90):.2f}); poll rounds "
                       f"median {np.median(polls):.0f} (min {polls.min()}, max {polls.max()})")
         if name == "fwd_conv" and fused:
-            bs = buf[grid * 72:].view(grid, 8, 4).cpu().numpy().astype(np.int64)
+            bs = buf[grid * 72:grid * 104].view(grid, 8, 4).cpu().numpy().astype(np.int64)
             t0w = r[:, :waves, 0].min(axis=1)
             relb = (bs - t0w[:, None, None]) * 10 / 1000.0
             for k2, label in enumerate(["bwd dC2 ready", "bwd wgrad done", "bwd dgrad done", "bwd reduced"]):
                 vals = [np.median(relb[:, w, k2]) for w in range(waves)]
                 print(f"  {label:14s}" + " ".join(f"{v:6.2f}" for v in vals))
+            dg = buf[diag0:].view(grid, 8).cpu().numpy().astype(np.int64)
+            if (dg > 0).all():
+                reld = (dg - t0w[:, None]) * 10 / 1000.0
+                print("  bwd dgrad MFMAs" + " ".join(f"{np.median(reld[:, w]):6.2f}" for w in range(waves)))
+                # per SIMD (waves s and s + 4): the later wave's last dgrad MFMA -> both waves' dgrad done,
+                # i.e. the time the SIMD's MFMA pipe has nothing left but runs the epilogues
+                tail = np.maximum(relb[:, :4, 2], relb[:, 4:, 2]) - np.maximum(reld[:, :4], reld[:, 4:])
+                print("  exposed dgrad epilogue per SIMD (median / p90 us): " + "  ".join(
+                    f"{np.median(tail[:, s]):.2f}/{np.percentile(tail[:, s], 90):.2f}" for s in range(4)))
         print("  slot/wave " + " ".join(f"{w:>6d}" for w in range(waves)))
         for s, label in sorted(slots.items(), key=lambda kv: np.median(rel[:, 0, kv[0]])):
             vals = [np.median(rel[:, w, s]) if (r[:, w, s] > 0).all() else float("nan") for w in range(waves)]

@@ -35,7 +35,8 @@ def main():
     CATS = _cats(nfx)
     rows, cats, lasts = [], [], []
     for rep in range(int(os.environ.get("REPS", "20"))):
-        buf = torch.zeros(grid * 104 + nfx * 16, dtype=torch.int64, device=dev)
+        # (+ grid * 8 words: a -DTDL_DIAG_DGRAD_STAMP build stamps there, see stamps_mnist.py)
+        buf = torch.zeros(grid * 104 + nfx * 16 + grid * 8, dtype=torch.int64, device=dev)
         st._impl.set_stamps(buf)
         st.forward_backward(0)
         st.finalize(True)
@@ -43,7 +44,7 @@ def main():
         torch.cuda.synchronize()
         f = buf[:grid * 104].cpu().numpy().astype(np.int64)
         f = f[f > (1 << 32)]  # (time stamps only: the head's slot 4 holds a poll count)
-        x = buf[grid * 104:].view(nfx, 8, 2).cpu().numpy().astype(np.int64)
+        x = buf[grid * 104:grid * 104 + nfx * 16].view(nfx, 8, 2).cpu().numpy().astype(np.int64)
         t0 = f.min()
         xs0 = x[:, :, 0].min()
         cats.append([((x[lo:hi, :, 0].min() - xs0) / 100, (np.median(x[lo:hi, :, 0]) - xs0) / 100,
