@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "kernels/accum.h"
+#include "kernels/ema.h"
 #include "kernels/mnist_cnn.h"
 #include "kernels/ops.h"
 #include "kernels/optim.h"
@@ -289,6 +290,38 @@ void set_clip(tdl::OptimArgs& a, const OptTensor& gscale, const OptDouble& clipv
   a.clipvalue = clipvalue.has_value() ? (float)*clipvalue : 0.f;
 }
 
+// The weight-EMA operands of an update kernel (keras/optimizers.py device_ema): ema = the average slab E of
+// w's size, momentum = ema_momentum (E = f32(m) * E + f32(1 - m) * W_new, the subtraction in f64 here),
+// mode 0 none / 1 update E / 2 update E and store W = E.
+tdl::WeightEma ema_operands(const at::Tensor& w, const OptTensor& ema, double momentum, int64_t mode) {
+  TORCH_CHECK(mode >= 0 && mode <= 2, "ema_mode must be 0 (off), 1 (update E) or 2 (update E, W = E), got ", mode);
+  if (mode == 0) {
+    TORCH_CHECK(!ema.has_value(), "ema given with ema_mode 0");
+    return tdl::WeightEma{nullptr, 0.f, 0.f, 0};
+  }
+  TORCH_CHECK(ema.has_value(), "ema_mode ", mode, " needs the ema slab");
+  check_slab_f32(*ema, "ema");
+  TORCH_CHECK(ema->device() == w.device(), "ema and w must be on the same device");
+  TORCH_CHECK(ema->numel() == w.numel(), "slab size mismatch: w has ", w.numel(), " elements, ema has ", ema->numel());
+  TORCH_CHECK(momentum >= 0.0 && momentum <= 1.0, "ema_momentum must lie in [0, 1], got ", momentum);
+  const int64_t n = w.numel();
+  const char* pw = reinterpret_cast<const char*>(w.data_ptr());
+  const char* pe = reinterpret_cast<const char*>(ema->data_ptr());
+  TORCH_CHECK(n == 0 || pw + n * 4 <= pe || pe + n * 4 <= pw, "w and ema must be different, non-overlapping slabs");
+  return tdl::WeightEma{ema->data_ptr<float>(), (float)momentum, (float)(1.0 - momentum), (int)mode};
+}
+
+// The moving average of the weights as a launch of its own (csrc/kernels/ema.hip): mode 1 E = m E + c W, mode 2
+// also W = E.  max_blocks lowers the grid cap (tests and scripts/bench_ema.py only).  Empty slabs launch nothing.
+void weight_ema(at::Tensor w, at::Tensor e, double m, int64_t mode, c10::optional<int64_t> max_blocks) {
+  check_slab_f32(w, "w");
+  TORCH_CHECK(mode == 1 || mode == 2, "mode must be 1 (update E) or 2 (update E, W = E), got ", mode);
+  const tdl::WeightEma x = ema_operands(w, e, m, mode);
+  const int64_t mb = max_blocks.value_or(tdl::kEmaMaxBlocks);
+  TORCH_CHECK(mb >= 1 && mb <= tdl::kEmaMaxBlocks, "max_blocks must lie in [1, ", tdl::kEmaMaxBlocks, "]");
+  tdl::weight_ema_apply(w.data_ptr<float>(), x.e, w.numel(), x.m, x.c, x.mode, cur_stream(), (int)mb);
+}
+
 // Global gradient norm of a flat f32 slab and the clip scale (csrc/kernels/clip.hip, two launches):
 // out[0] = scale = min(1, clipnorm / (norm + 1e-12)), out[1] = norm = |clamp(g, +-clipvalue)|_2 (f32 words;
 // the sum in f64, in an order that depends on g.numel() alone).  partials: f64 scratch of
@@ -333,33 +366,36 @@ void grad_accum(at::Tensor g, at::Tensor a, int64_t mode, double c, bool zero_gr
                         (int)mb);
 }
 
-void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad, OptTensor gscale, OptDouble clipvalue) {
+void sgd(at::Tensor w, at::Tensor g, at::Tensor lr, bool zero_grad, OptTensor gscale, OptDouble clipvalue,
+         OptTensor ema, double ema_momentum, int64_t ema_mode) {
   check_slab_f32(w, "w");
   check_slab_f32(g, "g");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel());
   const float cv = clipvalue.has_value() ? (float)*clipvalue : 0.f;
+  const tdl::WeightEma x = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::sgd_apply(w.data_ptr<float>(), g.data_ptr<float>(), lr.data_ptr<float>(), w.numel(), cur_stream(), zero_grad,
-                 gscale_ptr(gscale), clipvalue.has_value() ? &cv : nullptr);
+                 gscale_ptr(gscale), clipvalue.has_value() ? &cv : nullptr, &x);
 }
 
 void sgd_momentum(at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor lr, double m, bool nesterov, bool zero_grad,
-                  OptTensor gscale, OptDouble clipvalue) {
+                  OptTensor gscale, OptDouble clipvalue, OptTensor ema, double ema_momentum, int64_t ema_mode) {
   check_slab_f32(w, "w");
   check_slab_f32(g, "g");
   check_slab_f32(v, "v");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(w.numel() == g.numel() && v.numel() == w.numel());
   const float cv = clipvalue.has_value() ? (float)*clipvalue : 0.f;
+  const tdl::WeightEma x = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::sgd_momentum_apply(w.data_ptr<float>(), g.data_ptr<float>(), v.data_ptr<float>(), lr.data_ptr<float>(),
                           (float)m, nesterov, w.numel(), cur_stream(), zero_grad, gscale_ptr(gscale),
-                          clipvalue.has_value() ? &cv : nullptr);
+                          clipvalue.has_value() ? &cv : nullptr, &x);
 }
 
 // Flat-slab Adam / AdamW (+AMSGrad): state m, v (vhat), device lr and execution-start step t0
 void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<at::Tensor> vhat, at::Tensor lr,
           at::Tensor t0, int64_t t_add, double b1, double b2, double eps, double wd, OptTensor gscale,
-          OptDouble clipvalue) {
+          OptDouble clipvalue, OptTensor ema, double ema_momentum, int64_t ema_mode) {
   for (auto* t : {&w, &g, &m, &v}) check_slab_f32(*t, "adam operand");
   for (auto* t : {&lr, &t0}) check_cuda_f32(*t, "adam operand");
   TORCH_CHECK(g.numel() == w.numel() && m.numel() == w.numel() && v.numel() == w.numel());
@@ -374,12 +410,14 @@ void adam(at::Tensor w, at::Tensor g, at::Tensor m, at::Tensor v, c10::optional<
   a.lr = lr.data_ptr<float>(); a.t0 = t0.data_ptr<float>(); a.t_add = (int)t_add; a.n = w.numel();
   a.b1 = (float)b1; a.b2 = (float)b2; a.eps = (float)eps; a.wd = (float)wd;
   set_clip(a, gscale, clipvalue);
+  a.ema = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::adam_apply(a, cur_stream());
 }
 
 // Flat-slab RMSprop (+momentum, centered)
 void rmsprop(at::Tensor w, at::Tensor g, at::Tensor rms, c10::optional<at::Tensor> mom, c10::optional<at::Tensor> mg,
-             at::Tensor lr, double rho, double momentum, double eps, OptTensor gscale, OptDouble clipvalue) {
+             at::Tensor lr, double rho, double momentum, double eps, OptTensor gscale, OptDouble clipvalue,
+             OptTensor ema, double ema_momentum, int64_t ema_mode) {
   for (auto* t : {&w, &g, &rms}) check_slab_f32(*t, "rmsprop operand");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && rms.numel() == w.numel());
@@ -389,12 +427,13 @@ void rmsprop(at::Tensor w, at::Tensor g, at::Tensor rms, c10::optional<at::Tenso
   if (mg.has_value()) { check_slab_f32(*mg, "mg"); TORCH_CHECK(mg->numel() == w.numel()); a.s2 = mg->data_ptr<float>(); a.flags |= 2; }
   a.lr = lr.data_ptr<float>(); a.n = w.numel(); a.b1 = (float)rho; a.b2 = (float)momentum; a.eps = (float)eps;
   set_clip(a, gscale, clipvalue);
+  a.ema = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::rmsprop_apply(a, cur_stream());
 }
 
 // Flat-slab Adagrad
 void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double eps, OptTensor gscale,
-             OptDouble clipvalue) {
+             OptDouble clipvalue, OptTensor ema, double ema_momentum, int64_t ema_mode) {
   for (auto* t : {&w, &g, &acc}) check_slab_f32(*t, "adagrad operand");
   check_cuda_f32(lr, "lr");
   TORCH_CHECK(g.numel() == w.numel() && acc.numel() == w.numel());
@@ -402,6 +441,7 @@ void adagrad(at::Tensor w, at::Tensor g, at::Tensor acc, at::Tensor lr, double e
   a.w = w.data_ptr<float>(); a.g = g.data_ptr<float>(); a.s0 = acc.data_ptr<float>();
   a.lr = lr.data_ptr<float>(); a.n = w.numel(); a.eps = (float)eps;
   set_clip(a, gscale, clipvalue);
+  a.ema = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::adagrad_apply(a, cur_stream());
 }
 
@@ -572,7 +612,8 @@ void lamb_ratio(const LayerTables& T, at::Tensor partials, at::Tensor ratio, at:
 
 // launch 3
 void lars_update(const LayerTables& T, at::Tensor w, at::Tensor g, at::Tensor v, at::Tensor ratio, at::Tensor lr,
-                 double momentum, bool nesterov, OptTensor gscale, OptDouble clipvalue) {
+                 double momentum, bool nesterov, OptTensor gscale, OptDouble clipvalue, OptTensor ema,
+                 double ema_momentum, int64_t ema_mode) {
   tdl::LayerArgs a = layer_args(T);
   a.w = layer_slab(w, T, "w");
   a.g = layer_slab(g, T, "g");
@@ -584,11 +625,13 @@ void lars_update(const LayerTables& T, at::Tensor w, at::Tensor g, at::Tensor v,
   a.b1 = (float)momentum;
   a.nesterov = nesterov ? 1 : 0;
   set_layer_clip(a, gscale, clipvalue);
+  a.ema = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::lars_apply(a, cur_stream());
 }
 
 void lamb_update(const LayerTables& T, at::Tensor w, at::Tensor m, at::Tensor v, at::Tensor ratio, at::Tensor lr,
-                 at::Tensor t0, int64_t t_add, double b1, double b2, double eps) {
+                 at::Tensor t0, int64_t t_add, double b1, double b2, double eps, OptTensor ema, double ema_momentum,
+                 int64_t ema_mode) {
   tdl::LayerArgs a = layer_args(T);
   a.w = layer_slab(w, T, "w");
   a.s0 = layer_slab(m, T, "m");
@@ -598,6 +641,7 @@ void lamb_update(const LayerTables& T, at::Tensor w, at::Tensor m, at::Tensor v,
   TORCH_CHECK(lr.numel() >= 1, "lr must hold the learning rate");
   a.lr = lr.data_ptr<float>();
   set_lamb(a, t0, t_add, b1, b2, eps);
+  a.ema = ema_operands(w, ema, ema_momentum, ema_mode);
   tdl::lamb_apply(a, cur_stream());
 }
 
@@ -654,22 +698,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "gradient accumulation micro-step: mode 0 a = g, 1 a += g, 2 g = (a + g) * c (zero_grad: g := 0, modes 0/1)",
         pybind11::arg("g"), pybind11::arg("a"), pybind11::arg("mode"), pybind11::arg("c"),
         pybind11::arg("zero_grad") = false, pybind11::arg("max_blocks") = none);
+  m.attr("EMA_MAX_BLOCKS") = (int64_t)tdl::kEmaMaxBlocks;    // grid cap of k_weight_ema
+  m.attr("EMA_BLOCK_ELEMS") = (int64_t)tdl::kEmaBlockElems;  // elements a workgroup handles per grid pass
+  m.def("weight_ema", &weight_ema,
+        "moving average of the weights: mode 1 e = f32(m) e + f32(1 - m) w, mode 2 also w = e (three f32 roundings)",
+        pybind11::arg("w"), pybind11::arg("e"), pybind11::arg("m"), pybind11::arg("mode"),
+        pybind11::arg("max_blocks") = none);
   m.def("sgd", &sgd, "w -= lr * g over a flat slab (zero_grad: g := 0 afterwards)", pybind11::arg("w"),
         pybind11::arg("g"), pybind11::arg("lr"), pybind11::arg("zero_grad") = false,
-        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   m.def("sgd_momentum", &sgd_momentum, "Keras momentum SGD over a flat slab (zero_grad: g := 0 afterwards)",
         pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("v"), pybind11::arg("lr"), pybind11::arg("m"),
         pybind11::arg("nesterov"), pybind11::arg("zero_grad") = false, pybind11::arg("gscale") = none,
-        pybind11::arg("clipvalue") = none);
+        pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   m.def("adam", &adam, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("m"), pybind11::arg("v"),
         pybind11::arg("vhat"), pybind11::arg("lr"), pybind11::arg("t0"), pybind11::arg("t_add"), pybind11::arg("b1"),
         pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("wd") = 0.0, pybind11::arg("gscale") = none,
-        pybind11::arg("clipvalue") = none);
+        pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   m.def("rmsprop", &rmsprop, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("rms"), pybind11::arg("mom"),
         pybind11::arg("mg"), pybind11::arg("lr"), pybind11::arg("rho"), pybind11::arg("momentum"), pybind11::arg("eps"),
-        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+        pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   m.def("adagrad", &adagrad, pybind11::arg("w"), pybind11::arg("g"), pybind11::arg("acc"), pybind11::arg("lr"),
-        pybind11::arg("eps"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+        pybind11::arg("eps"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   // layer-wise optimizers (csrc/kernels/layerwise.hip): host-validated tables, then three launches per step
   m.attr("LAYER_CHUNK") = (int64_t)tdl::kLayerChunk;  // largest chunk of a variable (one workgroup)
   pybind11::class_<LayerTables>(m, "LayerTables")
@@ -701,10 +756,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("norms"));
   m.def("lars_update", &lars_update, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("g"),
         pybind11::arg("v"), pybind11::arg("ratio"), pybind11::arg("lr"), pybind11::arg("momentum"),
-        pybind11::arg("nesterov"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none);
+        pybind11::arg("nesterov"), pybind11::arg("gscale") = none, pybind11::arg("clipvalue") = none, pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   m.def("lamb_update", &lamb_update, pybind11::arg("tables"), pybind11::arg("w"), pybind11::arg("m"),
         pybind11::arg("v"), pybind11::arg("ratio"), pybind11::arg("lr"), pybind11::arg("t0"), pybind11::arg("t_add"),
-        pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"));
+        pybind11::arg("b1"), pybind11::arg("b2"), pybind11::arg("eps"), pybind11::arg("ema") = none,
+        pybind11::arg("ema_momentum") = 0.0, pybind11::arg("ema_mode") = 0);
   register_ops(m);
   register_comm(m);
   register_rccl(m);

@@ -280,7 +280,10 @@ __global__ __launch_bounds__(64) void k_layer_ratio(LayerArgs a) {
 
 // ---------------------------------------------------------------------------------------- launch 3
 // LARS: momentum SGD (lars_one) with lr -> s = lr * ratio[var], g -> d = g' + wd w
-template <int CH, bool CLIP>
+// EMA (both apply kernels): the moving average of the weights (WeightEma, optim.h) is loaded with the other
+// operands and stored where w is; on an overwrite step it is what is stored as w.  Elements between two
+// variables (the layout's alignment gaps) belong to no chunk: neither w nor e of them is touched.
+template <int CH, bool CLIP, bool EMA>
 __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
   constexpr int kU = CH / (kT * 4);
   const GradClip gc(CLIP ? a.gscale : nullptr, a.clipvalue, CLIP ? a.clip : 0);
@@ -293,15 +296,20 @@ __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
   float* __restrict__ w = a.w + c.start;
   const float* __restrict__ g = a.g + c.start;
   float* __restrict__ v = a.s0 + c.start;
+  float* __restrict__ e = EMA ? a.ema.e + c.start : nullptr;
   const int tid = threadIdx.x;
   if (c.len == CH) {
-    f4 wv[kU], gv[kU], vv[kU];
+    f4 wv[kU], gv[kU], vv[kU], ev[kU];
 #pragma unroll
     for (int u = 0; u < kU; ++u) wv[u] = ld4(w + (u * kT + tid) * 4);
 #pragma unroll
     for (int u = 0; u < kU; ++u) gv[u] = ld4(g + (u * kT + tid) * 4);
 #pragma unroll
     for (int u = 0; u < kU; ++u) vv[u] = ld4(v + (u * kT + tid) * 4);
+    if constexpr (EMA) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) ev[u] = ld4(e + (u * kT + tid) * 4);
+    }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
       const f4 gg = grad_of<CLIP>(gc, gv[u]);
@@ -312,6 +320,7 @@ __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
         wv[u][k] = wk;
         vv[u][k] = vk;
       }
+      if constexpr (EMA) wv[u] = ema_store(a.ema, e + (u * kT + tid) * 4, ev[u], wv[u]);
       st4(w + (u * kT + tid) * 4, wv[u]);
       st4(v + (u * kT + tid) * 4, vv[u]);
     }
@@ -322,6 +331,8 @@ __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
       if (i4 + 3 < c.len) {
         f4 wv = ld4(w + i4), vv = ld4(v + i4);
         const f4 gg = grad_of<CLIP>(gc, ld4(g + i4));
+        f4 ev = zero4();
+        if constexpr (EMA) ev = ld4(e + i4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           float wk = wv[k], vk = vv[k];
@@ -329,13 +340,17 @@ __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
           wv[k] = wk;
           vv[k] = vk;
         }
+        if constexpr (EMA) wv = ema_store(a.ema, e + i4, ev, wv);
         st4(w + i4, wv);
         st4(v + i4, vv);
       } else {
         for (int j = i4; j < c.len; ++j) {
           float wj = w[j], vj = v[j];
+          float ej = 0.f;
+          if constexpr (EMA) ej = e[j];
           lars_one(wj, vj, grad_of<CLIP>(gc, g[j]), wd, mu, s, nesterov);
           v[j] = vj;
+          if constexpr (EMA) wj = ema_store(a.ema, e + j, ej, wj);
           w[j] = wj;
         }
       }
@@ -344,7 +359,7 @@ __global__ __launch_bounds__(kT) void k_lars_apply(LayerArgs a) {
 }
 
 // LAMB: w -= s u, u re-evaluated from the m, v of launch 1 (g is not loaded)
-template <int CH>
+template <int CH, bool EMA>
 __global__ __launch_bounds__(kT) void k_lamb_apply(LayerArgs a) {
   constexpr int kU = CH / (kT * 4);
   const Chunk c(a.chunks);
@@ -355,19 +370,25 @@ __global__ __launch_bounds__(kT) void k_lamb_apply(LayerArgs a) {
   float* __restrict__ w = a.w + c.start;
   const float* __restrict__ m = a.s0 + c.start;
   const float* __restrict__ v = a.s1 + c.start;
+  float* __restrict__ e = EMA ? a.ema.e + c.start : nullptr;
   const int tid = threadIdx.x;
   if (c.len == CH) {
-    f4 wv[kU], mv[kU], vv[kU];
+    f4 wv[kU], mv[kU], vv[kU], ev[kU];
 #pragma unroll
     for (int u = 0; u < kU; ++u) wv[u] = ld4(w + (u * kT + tid) * 4);
 #pragma unroll
     for (int u = 0; u < kU; ++u) mv[u] = ld4(m + (u * kT + tid) * 4);
 #pragma unroll
     for (int u = 0; u < kU; ++u) vv[u] = ld4(v + (u * kT + tid) * 4);
+    if constexpr (EMA) {
+#pragma unroll
+      for (int u = 0; u < kU; ++u) ev[u] = ld4(e + (u * kT + tid) * 4);
+    }
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) wv[u][k] = lamb_step(wv[u][k], s, lamb_u(mv[u][k], vv[u][k], wv[u][k], corr, a.eps, wd));
+      if constexpr (EMA) wv[u] = ema_store(a.ema, e + (u * kT + tid) * 4, ev[u], wv[u]);
       st4(w + (u * kT + tid) * 4, wv[u]);
     }
   } else {
@@ -377,11 +398,20 @@ __global__ __launch_bounds__(kT) void k_lamb_apply(LayerArgs a) {
       if (i4 + 3 < c.len) {
         f4 wv = ld4(w + i4);
         const f4 mv = ld4(m + i4), vv = ld4(v + i4);
+        f4 ev = zero4();
+        if constexpr (EMA) ev = ld4(e + i4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) wv[k] = lamb_step(wv[k], s, lamb_u(mv[k], vv[k], wv[k], corr, a.eps, wd));
+        if constexpr (EMA) wv = ema_store(a.ema, e + i4, ev, wv);
         st4(w + i4, wv);
       } else {
-        for (int j = i4; j < c.len; ++j) w[j] = lamb_step(w[j], s, lamb_u(m[j], v[j], w[j], corr, a.eps, wd));
+        for (int j = i4; j < c.len; ++j) {
+          float ej = 0.f;
+          if constexpr (EMA) ej = e[j];
+          float wj = lamb_step(w[j], s, lamb_u(m[j], v[j], w[j], corr, a.eps, wd));
+          if constexpr (EMA) wj = ema_store(a.ema, e + j, ej, wj);
+          w[j] = wj;
+        }
       }
     }
   }
@@ -429,15 +459,23 @@ void lars_apply(const LayerArgs& a, hipStream_t s) {
   const dim3 grid((unsigned)a.C), block(kT);
   with_chunk(a.chunk, [&](auto ch) {
     constexpr int CH = decltype(ch)::value;
-    if (clipped(a)) hipLaunchKernelGGL((k_lars_apply<CH, true>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_lars_apply<CH, false>), grid, block, 0, s, a);
+    if (a.ema.mode != 0) {
+      if (clipped(a)) hipLaunchKernelGGL((k_lars_apply<CH, true, true>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_lars_apply<CH, false, true>), grid, block, 0, s, a);
+    } else {
+      if (clipped(a)) hipLaunchKernelGGL((k_lars_apply<CH, true, false>), grid, block, 0, s, a);
+      else hipLaunchKernelGGL((k_lars_apply<CH, false, false>), grid, block, 0, s, a);
+    }
   });
 }
 
 void lamb_apply(const LayerArgs& a, hipStream_t s) {
   if (a.C <= 0) return;
+  const dim3 grid((unsigned)a.C), block(kT);
   with_chunk(a.chunk, [&](auto ch) {
-    hipLaunchKernelGGL((k_lamb_apply<decltype(ch)::value>), dim3((unsigned)a.C), dim3(kT), 0, s, a);
+    constexpr int CH = decltype(ch)::value;
+    if (a.ema.mode != 0) hipLaunchKernelGGL((k_lamb_apply<CH, true>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((k_lamb_apply<CH, false>), grid, block, 0, s, a);
   });
 }
 

@@ -138,11 +138,14 @@ void mnist_finalize_x(const MnistArgs& a, bool apply_sgd, hipStream_t s);
 // zero_g: g is zeroed after its use (the next step accumulates into it without a fill launch)
 // gscale (device scale word of clip_norm, optim.h) / clipvalue (HOST pointer to the clamp bound): gradient
 // clipping g' = clamp(g, +-clipvalue) * *gscale where g is loaded; either may be null
+// ema (optim.h; null or mode 0: none): the moving average of the weights, kept where w is stored
+struct WeightEma;
 void sgd_apply(float* w, const float* g, const float* lr, int64_t n, hipStream_t s, bool zero_g = false,
-               const float* gscale = nullptr, const float* clipvalue = nullptr);
+               const float* gscale = nullptr, const float* clipvalue = nullptr, const WeightEma* ema = nullptr);
 // Momentum SGD (Keras semantics): v = m*v - lr*g ; w += v  (nesterov: w += m*v - lr*g)
 void sgd_momentum_apply(float* w, const float* g, float* v, const float* lr, float momentum,
                         bool nesterov, int64_t n, hipStream_t s, bool zero_g = false,
-                        const float* gscale = nullptr, const float* clipvalue = nullptr);
+                        const float* gscale = nullptr, const float* clipvalue = nullptr,
+                        const WeightEma* ema = nullptr);
 
 }  // namespace tdl

@@ -1841,39 +1841,56 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
 // (g is not __restrict__: gz aliases it)
 // CLIP: g' = clamp(g, +-clipvalue) * *gscale where g is loaded (GradClip, optim.h); the unclipped
 // instantiations contain none of it
-template <bool CLIP>
+// EMA: the moving average of the weights (WeightEma, optim.h) is loaded with the other operands and stored
+// where w is; on an overwrite step it is what is stored as w.  The instantiations without it contain none of it
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void k_sgd(float* __restrict__ w, const float* g, const float* __restrict__ lrp,
-                                             int64_t n, float* gz, const float* gscale, float clipvalue, int clip) {
+                                             int64_t n, float* gz, const float* gscale, float clipvalue, int clip,
+                                             WeightEma ema) {
   const GradClip gc(CLIP ? gscale : nullptr, clipvalue, CLIP ? clip : 0);
   const float lr = *lrp;
   const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     f4 wv = ld4(w + i4);
     const f4 gv = grad_of<CLIP>(gc, ld4(g + i4));
+    f4 ev = zero4();
+    if constexpr (EMA) ev = ld4(ema.e + i4);
     wv -= lr * gv;
+    if constexpr (EMA) wv = ema_store(ema, ema.e + i4, ev, wv);
     st4(w + i4, wv);
     if (gz != nullptr) st4(gz + i4, zero4());
   } else {
     for (int64_t j = i4; j < n; ++j) {
-      w[j] -= lr * grad_of<CLIP>(gc, g[j]);
+      if constexpr (EMA) {
+        const float ej = ema.e[j];
+        float wj = w[j];
+        wj -= lr * grad_of<CLIP>(gc, g[j]);
+        w[j] = ema_store(ema, ema.e + j, ej, wj);
+      } else {
+        w[j] -= lr * grad_of<CLIP>(gc, g[j]);
+      }
       if (gz != nullptr) gz[j] = 0.f;
     }
   }
 }
 
-template <bool CLIP>
+template <bool CLIP, bool EMA>
 __global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ w, const float* g,
                                                       float* __restrict__ v, const float* __restrict__ lrp,
                                                       float m, int nesterov, int64_t n, float* gz,
-                                                      const float* gscale, float clipvalue, int clip) {
+                                                      const float* gscale, float clipvalue, int clip,
+                                                      WeightEma ema) {
   const GradClip gc(CLIP ? gscale : nullptr, clipvalue, CLIP ? clip : 0);
   const float lr = *lrp;
   const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 + 3 < n) {
     f4 wv = ld4(w + i4), vv = ld4(v + i4);
     const f4 gv = grad_of<CLIP>(gc, ld4(g + i4));
+    f4 ev = zero4();
+    if constexpr (EMA) ev = ld4(ema.e + i4);
     vv = m * vv - lr * gv;
     wv += nesterov ? (m * vv - lr * gv) : vv;
+    if constexpr (EMA) wv = ema_store(ema, ema.e + i4, ev, wv);
     st4(w + i4, wv);
     st4(v + i4, vv);
     if (gz != nullptr) st4(gz + i4, zero4());
@@ -1882,7 +1899,14 @@ __global__ __launch_bounds__(256) void k_sgd_momentum(float* __restrict__ w, con
       const float gj = grad_of<CLIP>(gc, g[j]);
       const float vj = m * v[j] - lr * gj;
       v[j] = vj;
-      w[j] += nesterov ? (m * vj - lr * gj) : vj;
+      if constexpr (EMA) {
+        const float ej = ema.e[j];
+        float wj = w[j];
+        wj += nesterov ? (m * vj - lr * gj) : vj;
+        w[j] = ema_store(ema, ema.e + j, ej, wj);
+      } else {
+        w[j] += nesterov ? (m * vj - lr * gj) : vj;
+      }
       if (gz != nullptr) gz[j] = 0.f;
     }
   }
@@ -1944,32 +1968,43 @@ void mnist_finalize_x(const MnistArgs& a, bool apply_sgd, hipStream_t s) {
     default: go(std::integral_constant<int, 1>{}); break;
   }
 }
+namespace {
+// k(std::bool_constant<CLIP>, std::bool_constant<EMA>) for the operands present
+template <class F>
+void with_clip_ema(bool clip, bool ema, F f) {
+  if (clip)
+    ema ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  else
+    ema ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
+}
+}  // namespace
 void sgd_apply(float* w, const float* g, const float* lr, int64_t n, hipStream_t s, bool zero_g,
-               const float* gscale, const float* clipvalue) {
+               const float* gscale, const float* clipvalue, const WeightEma* ema) {
   if (n <= 0) return;
   const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
   float* gz = zero_g ? const_cast<float*>(g) : nullptr;
   const float cv = clipvalue != nullptr ? *clipvalue : 0.f;
   const int clip = clipvalue != nullptr;
-  if (gscale != nullptr || clip)
-    hipLaunchKernelGGL(k_sgd<true>, grid, dim3(256), 0, s, w, g, lr, n, gz, gscale, cv, clip);
-  else
-    hipLaunchKernelGGL(k_sgd<false>, grid, dim3(256), 0, s, w, g, lr, n, gz, gscale, cv, clip);
+  const WeightEma em = ema != nullptr ? *ema : WeightEma{nullptr, 0.f, 0.f, 0};
+  with_clip_ema(gscale != nullptr || clip, em.mode != 0, [&](auto c, auto e) {
+    hipLaunchKernelGGL((k_sgd<decltype(c)::value, decltype(e)::value>), grid, dim3(256), 0, s, w, g, lr, n, gz, gscale,
+                       cv, clip, em);
+  });
 }
 void sgd_momentum_apply(float* w, const float* g, float* v, const float* lr, float momentum, bool nesterov,
-                        int64_t n, hipStream_t s, bool zero_g, const float* gscale, const float* clipvalue) {
+                        int64_t n, hipStream_t s, bool zero_g, const float* gscale, const float* clipvalue,
+                        const WeightEma* ema) {
   if (n <= 0) return;
   const dim3 grid((unsigned)(((n + 3) / 4 + 255) / 256));
   float* gz = zero_g ? const_cast<float*>(g) : nullptr;
   const float cv = clipvalue != nullptr ? *clipvalue : 0.f;
   const int clip = clipvalue != nullptr;
   const int nest = nesterov ? 1 : 0;
-  if (gscale != nullptr || clip)
-    hipLaunchKernelGGL(k_sgd_momentum<true>, grid, dim3(256), 0, s, w, g, v, lr, momentum, nest, n, gz, gscale, cv,
-                       clip);
-  else
-    hipLaunchKernelGGL(k_sgd_momentum<false>, grid, dim3(256), 0, s, w, g, v, lr, momentum, nest, n, gz, gscale, cv,
-                       clip);
+  const WeightEma em = ema != nullptr ? *ema : WeightEma{nullptr, 0.f, 0.f, 0};
+  with_clip_ema(gscale != nullptr || clip, em.mode != 0, [&](auto c, auto e) {
+    hipLaunchKernelGGL((k_sgd_momentum<decltype(c)::value, decltype(e)::value>), grid, dim3(256), 0, s, w, g, v, lr,
+                       momentum, nest, n, gz, gscale, cv, clip, em);
+  });
 }
 
 }  // namespace tdl

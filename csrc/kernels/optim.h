@@ -10,6 +10,16 @@
 
 namespace tdl {
 
+// The moving average of the weights (use_ema, keras/optimizers.py), kept by the kernel that stores the new
+// weight: E = m * E + c * W_new, two products and a sum, three f32 roundings, never contracted (ema_fold).
+// mode 0: off (e is null); 1: update E; 2: update E and store W = E_new (an overwrite step).  The mode of a
+// step is known to the host at launch and at capture time: a launch argument, never a device counter.
+struct WeightEma {
+  float* e;
+  float m, c;  // float32(ema_momentum), float32(1 - ema_momentum) with the subtraction done in f64 on the host
+  int mode;
+};
+
 struct OptimArgs {
   float* w;
   const float* g;
@@ -28,6 +38,7 @@ struct OptimArgs {
   const float* gscale;  // device scale word written by clip_norm (or null)
   float clipvalue;      // clamp bound (read only when clip != 0)
   int clip;             // 1: clamp by clipvalue
+  WeightEma ema;        // mode 0: none, and the kernel is the instantiation without it
 };
 
 #if defined(__HIPCC__)  // device code (the bindings include this header with the host compiler)
@@ -52,6 +63,28 @@ template <bool CLIP>
 __device__ __forceinline__ f4 grad_of(const GradClip& c, f4 g) {
   if constexpr (CLIP) return f4{c(g[0]), c(g[1]), c(g[2]), c(g[3])};
   return g;
+}
+// The new average of one element.  Contraction is off for exactly this expression: the update formulas
+// around a call keep the fused forms hipcc gives them.
+__device__ __forceinline__ float ema_fold(const WeightEma& x, float e, float w) {
+#pragma clang fp contract(off)
+  const float me = x.m * e, cw = x.c * w;
+  return me + cw;
+}
+__device__ __forceinline__ f4 ema_fold(const WeightEma& x, f4 e, f4 w) {
+  return f4{ema_fold(x, e[0], w[0]), ema_fold(x, e[1], w[1]), ema_fold(x, e[2], w[2]), ema_fold(x, e[3], w[3])};
+}
+// Where an EMA instantiation stores w: e becomes the new average and is stored at pe; on an overwrite step
+// the caller then stores the returned value, e's, as the weight.
+__device__ __forceinline__ f4 ema_store(const WeightEma& x, float* pe, f4 e, f4 w) {
+  e = ema_fold(x, e, w);
+  st4(pe, e);
+  return x.mode == 2 ? e : w;
+}
+__device__ __forceinline__ float ema_store(const WeightEma& x, float* pe, float e, float w) {
+  e = ema_fold(x, e, w);
+  *pe = e;
+  return x.mode == 2 ? e : w;
 }
 #endif
 
@@ -110,6 +143,7 @@ struct LayerArgs {
   const float* gscale;  // gradient clipping, as in OptimArgs
   float clipvalue;
   int clip;
+  WeightEma ema;        // the moving average, as in OptimArgs (read by the apply kernels, launch 3)
 };
 void layer_sums_apply(const LayerArgs& a, bool lamb, hipStream_t s);   // launch 1
 void layer_ratio_apply(const LayerArgs& a, bool lamb, hipStream_t s);  // launch 2

@@ -72,8 +72,25 @@ def execution_starts(steps: int, K: int, accum_steps: int = 1) -> List[Tuple[int
 
 def accum_key(opt, key: tuple, t_add: int = 0) -> tuple:
     """Key of the execution graph that starts ``t_add`` micro-steps from now; with gradient
-    accumulation it carries the execution's starting phase (every step's mode is baked in)."""
+    accumulation it carries the execution's starting phase (every step's mode is baked in).  With
+    a weight EMA that overwrites every f steps (``ema_overwrite_frequency``) the phase is taken mod
+    f: f is a multiple of the accumulation steps, so it tells both the accumulation phase and which
+    steps of the execution overwrite.  Unchanged with EMA off."""
+    if getattr(opt, "use_ema", False) and opt.ema_overwrite_frequency is not None:
+        return key + (("ema", (int(opt.iterations) + int(t_add)) % opt.ema_overwrite_frequency),)
     return key + (opt._accum_phase(t_add),) if opt._accumulating else key
+
+
+def phase_period(opt, K: int = 1) -> int:
+    """How many distinct starting phases the K-step executions of a run can have (the ``accum_steps``
+    of ``execution_starts``): the accumulation steps, or, with EMA overwrites on, the number of
+    distinct values of ``i K mod f``."""
+    if getattr(opt, "use_ema", False) and opt.ema_overwrite_frequency is not None:
+        import math
+
+        f = opt.ema_overwrite_frequency
+        return f // math.gcd(f, max(1, int(K)))
+    return opt.gradient_accumulation_steps or 1
 
 
 @contextlib.contextmanager

@@ -93,6 +93,8 @@ def eligible(model, dataset=None) -> Optional[str]:
         return "the extension has no clip_norm kernel (rebuild: python build_native.py)"
     if opt._accumulating and not hasattr(ops.hip(), "grad_accum"):
         return "the extension has no grad_accum kernel (rebuild: python build_native.py)"
+    if getattr(opt, "use_ema", False) and not hasattr(ops.hip(), "weight_ema"):
+        return "the extension has no weight_ema kernel (rebuild: python build_native.py)"
     if opt.weight_decay and not isinstance(opt, optimizers.Adam):
         return "decoupled weight decay is fused for Adam/AdamW only"
     kern = {"Adam": "adam", "AdamW": "adam", "RMSprop": "rmsprop", "Adagrad": "adagrad", "LARS": "layer_tables",
@@ -156,6 +158,7 @@ class FusedMnistTrainer(EX.Prefetching):
         self.optimizer = model.optimizer
         self.optimizer.set_layout(model._layout)
         self.optimizer.build(self.W.numel(), self.device)
+        self.optimizer.init_ema(self.W)  # (use_ema: E = W once, before any capture; a restored E is kept)
         self.K = max(1, int(model._steps_per_execution))
         self.metrics_dev = torch.zeros(4, dtype=torch.float32, device=self.device)
         self._steps = {}
@@ -240,7 +243,11 @@ class FusedMnistTrainer(EX.Prefetching):
         optimizer is never plain: finalize(False) -> all-reduce -> clip_norm -> update kernel.  Neither is
         an accumulating one (``gradient_accumulation_steps``): finalize(False) -> accumulate, and only the
         cycle's last micro-step goes on to the all-reduce and the update; step k's phase is that of
-        ``iterations + k`` (``iterations`` advances once per execution), baked in at capture."""
+        ``iterations + k`` (``iterations`` advances once per execution), baked in at capture.  A weight
+        EMA (``use_ema``) leaves plain SGD plain: the SGD inside finalize, the exchange in finalize and
+        all_reduce_sgd are kept and one ``weight_ema`` launch follows them (``ema_after``), so the R > 1
+        exchange stays in the finalize launch; every other optimizer's update kernel keeps the average
+        itself.  ``self.update_path`` names the path the last step took."""
         opt = self.optimizer
         if opt._accumulating:
             st.finalize(False)
@@ -250,15 +257,23 @@ class FusedMnistTrainer(EX.Prefetching):
         plain = self._plain_sgd
         if self.R == 1 and plain:
             st.finalize(True, keep_grad=False)  # (nothing reads G on this path)
+            self.update_path = "sgd-in-finalize"
+            opt.ema_after(self.W, k)
             return
         if self.R > 1 and plain and st.has_exchange:
             # fused backward: the finalize launch itself all-reduces over xGMI and applies SGD
             st.finalize(True, exchange=True, keep_grad=False)  # (G is not read on this path)
+            self.update_path = "exchange-in-finalize"
+            opt.ema_after(self.W, k)
             return
         st.finalize(False)
         if self.R > 1 and plain and self.comm.all_reduce_sgd(self.G, self.W, opt.lr_dev):
+            self.update_path = "all-reduce-sgd"
+            opt.ema_after(self.W, k)
             return
         self._reduce_and_update(k)
+
+    update_path = None  # how the last step updated W: one of the plain-SGD paths above or "update-kernel"
 
     def _train_step(self, st, off: int, global_b: int):
         """One whole step on the current stream.  R > 1 default (serial): forward + backward,
@@ -291,12 +306,17 @@ class FusedMnistTrainer(EX.Prefetching):
         st.finalize(False)
         if dense_fused and self.comm.all_reduce_sgd(G[:d0], W[:d0], lr):
             main.wait_stream(cs)
+            self.update_path = "overlap-all-reduce-sgd"
+            self.optimizer.ema_after(self.W, k)  # (main stream, both buckets have joined)
             return
         cs.wait_stream(main)
         with torch.cuda.stream(cs):
             self.comm.all_reduce(G[:d0], "sum")
         main.wait_stream(cs)
         self._update(0, d0 if dense_fused else None, k)
+        if dense_fused:
+            # (the conv bucket's k_sgd saw a slice and took no EMA operands: the whole slab now, both joined)
+            self.optimizer.ema_after(self.W, k)
 
     def _prepare_comm(self, st):
         """Collective set-up of the communicator's all-reduce channels for this step's buckets
@@ -409,7 +429,12 @@ class FusedMnistTrainer(EX.Prefetching):
         # (gradient clipping needs the whole reduced gradient before any update: never the SGD inside
         # finalize, all_reduce_sgd, the exchange-in-finalize channel or the two-bucket overlap; gradient
         # accumulation folds the local gradient first and updates on the cycle's last micro-step only)
+        # A weight EMA (use_ema) leaves plain SGD plain: the stand-alone weight_ema launch follows the plain update
+        # (_apply).  ``leave_plain_for_ema`` (scripts/bench_ema.py's measurement switch, never set by the engines)
+        # sends such an optimizer through k_sgd with the average inside instead.
         opt = self.optimizer
+        if getattr(opt, "use_ema", False) and getattr(self, "leave_plain_for_ema", False):
+            return False
         return type(opt).__name__ == "SGD" and opt.momentum == 0 and not opt._clipped and not opt._accumulating
 
     def _update(self, lo: int = 0, hi: Optional[int] = None, k: int = 0):
@@ -420,6 +445,7 @@ class FusedMnistTrainer(EX.Prefetching):
         W, G = self.W[lo:hi], self.G[lo:hi]
         if not opt.device_update(W, G, k):
             raise RuntimeError(f"fused trainer: {type(opt).__name__} has no device update on {W.device}")
+        self.update_path = "update-kernel"
 
     def _reduce_and_update(self, k: int):
         if self.R > 1:
@@ -497,7 +523,7 @@ class FusedMnistTrainer(EX.Prefetching):
         if b is None:
             return
         # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
-        starts = EX.execution_starts(steps, self.K, self.optimizer.gradient_accumulation_steps or 1)
+        starts = EX.execution_starts(steps, self.K, EX.phase_period(self.optimizer, self.K))
         for K, t_add in starts:
             for slot in range(self._nslots):
                 self._graph_for(K, b, slot, t_add)

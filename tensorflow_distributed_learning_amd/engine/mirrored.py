@@ -93,12 +93,16 @@ class _ReplicaFused(F.FusedMnistTrainer):
         mode = self.grp.mode
         if mode == "xchg" and st.has_exchange:
             st.finalize(True, exchange=True, keep_grad=False)
+            self.update_path = "exchange-in-finalize"
+            self.optimizer.ema_after(self.W, k)  # (use_ema: plain SGD stays plain, one launch follows)
             return
         if mode in ("xchg", "xgmi"):
             st.finalize(False)
             ch = self.grp.ar[self.r]
             if self._plain_sgd:
                 ch.all_reduce_sgd(self.G, self.W, self.optimizer.lr_dev, 1.0)
+                self.update_path = "all-reduce-sgd"
+                self.optimizer.ema_after(self.W, k)
             else:
                 ch.all_reduce(self.G, self.G, 1.0)
                 self._update(k=k)
@@ -279,6 +283,8 @@ class MirroredFusedTrainer(EX.Prefetching):
 
         dc = self.dc
         saved = [(s.W.clone(), s.G.clone()) for s in self.subs]
+        # (use_ema: the plain-SGD path under test is followed by the moving average's launch)
+        saved_ema = [{k: v.clone() for k, v in s.optimizer.slots().items() if k == "ema"} for s in self.subs]
         n = len(self.subs[0].X)
         try:
             steps = []
@@ -329,9 +335,11 @@ class MirroredFusedTrainer(EX.Prefetching):
         except Exception as e:  # noqa: BLE001 - any failure means the serial path
             return False, f"{type(e).__name__}: {e}"
         finally:
-            for s, (w, gr) in zip(self.subs, saved):
+            for s, (w, gr), ema in zip(self.subs, saved, saved_ema):
                 s.W.copy_(w)
                 s.G.copy_(gr)
+                for k, v in ema.items():
+                    s.optimizer.slots()[k].copy_(v)
             dc.synchronize()
 
     # ------------------------------------------------------------------ executions

@@ -147,6 +147,7 @@ class GenericTrainer:
         self.optimizer = model.optimizer
         self.optimizer.set_layout(model._layout)
         self.optimizer.build(self.W.numel(), self.device)
+        self.optimizer.init_ema(self.W)  # (use_ema: E = W once, before any capture; a restored E is kept)
         self.loss = model.loss
         self.loss_tracker = model._loss_tracker
         self.metrics = model.compiled_metrics
@@ -584,6 +585,8 @@ class GenericTrainer:
         key = (global_n,) + tuple((tuple(t.shape), t.dtype) for t in flat)
         if self.optimizer._accumulating:  # the accumulate mode is baked into the capture
             key += (("accum", self._accum_mode()),)
+        if self.optimizer.use_ema:  # so is the step's EMA mode (update E / also overwrite W)
+            key += (("ema", self.optimizer._ema_mode()),)
         ent = self._graphs.get(key)
         if ent is None:
             seen = self._seen.get(key, 0) + 1
@@ -687,8 +690,8 @@ class GenericTrainer:
             return
         # (an accumulating optimizer: one graph per starting phase the executions of this run will have)
         opt = self.optimizer
-        starts = EX.execution_starts(steps, max(1, self.model._steps_per_execution),
-                                     opt.gradient_accumulation_steps or 1)
+        spe = max(1, self.model._steps_per_execution)
+        starts = EX.execution_starts(steps, spe, EX.phase_period(opt, spe))
         n = max(k for k, _ in starts) * b
         if self._dev_idx is None or self._dev_idx.numel() < n:
             self._dev_upload(np.zeros(n, dtype=np.int32))

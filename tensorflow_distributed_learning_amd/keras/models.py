@@ -9,6 +9,7 @@ autograd engine otherwise (engine/trainer.py).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import sys
@@ -583,6 +584,13 @@ class Model(Layer):
         _fault.note_progress(busy=False)
         if hasattr(handler, "close"):  # stop an index producer, commit the epochs it consumed
             handler.close()
+        if getattr(self.optimizer, "use_ema", False):
+            # Keras' finalize_variable_values: W <- E once, after the last execution, on every replica (each
+            # holds the same E); validation and ModelCheckpoint during fit saw the live weights
+            for m in (trainer.models if group else [self]):
+                if m._W is not None:
+                    with (torch.cuda.device(m._W.device) if m._W.is_cuda else contextlib.nullcontext()):
+                        m.optimizer.finalize_slab(m._W)
         if os.environ.get("TDL_CHECK_REPLICAS", "1") == "1":
             self._check_replicas(trainer)
         cb_list.on_train_end(logs)

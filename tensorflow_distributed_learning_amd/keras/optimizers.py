@@ -31,6 +31,21 @@ launch of ``_C.grad_accum``, csrc/kernels/accum.hip, on the GPU), and only the k
 clips and updates, on the cycle's mean gradient.  ``iterations`` counts micro-steps (Keras 3's counting) and
 the phase of a micro-step is ``iterations mod k``, known to the host at launch and at capture time: no device
 counter.  Keras is not installed where this was written: parity with its implementation is unpinned.
+
+Weight EMA (``use_ema=True``, ``ema_momentum``, ``ema_overwrite_frequency`` on every optimizer): one more f32
+slab, the slot ``"ema"`` (``E``), starts as a copy of the weights before the first update (``init_ema``) and
+follows every weight update, element for element in f32: ``E = float32(m) * E + float32(1 - m) * W_new``, two
+products and a sum, three roundings, no contraction (numpy's ``np.float32(m) * E + np.float32(1 - m) * W`` gives
+the bits; the torch form of it is the CPU implementation).  On the GPU every update kernel has an instantiation
+that loads ``e`` with its operands and stores the new average where it stores ``w`` (``device_ema`` hands it the
+operands, no extra launch); an update done elsewhere -- the SGD inside the fused step's finalize or an xGMI
+all-reduce, a torch formula -- is followed by ``ema_after``: one launch of ``_C.weight_ema``
+(csrc/kernels/ema.hip).  With ``ema_overwrite_frequency=f`` the update whose 1-based step count
+``iterations + 1`` is a multiple of f also stores ``W = E`` (``_ema_mode``: 2 on such a step, else 1): the host
+knows it at launch and at capture time, so it is a kernel mode and part of the execution-graph key, never a device
+counter.  With gradient accumulation ``E`` moves on apply micro-steps only and f must be a multiple of k.
+``finalize_variable_values`` (end of ``fit``, custom loops) stores ``W = E`` once.  Keras / TF are not installed
+where this was written: parity with their implementation is unpinned.
 """
 from __future__ import annotations
 
@@ -44,12 +59,24 @@ from . import schedules as _sched
 
 class Optimizer:
     def __init__(self, learning_rate=0.001, name="Optimizer", clipnorm=None, clipvalue=None, global_clipnorm=None,
-                 weight_decay=None, gradient_accumulation_steps=None, **kwargs):
+                 weight_decay=None, gradient_accumulation_steps=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None, **kwargs):
         self.name = name
         k = gradient_accumulation_steps
         if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
             raise ValueError(f"gradient_accumulation_steps must be None or an integer >= 1, got {k!r}")
         self.gradient_accumulation_steps = k
+        # (the momentum and the frequency are validated even when use_ema is off, where nothing reads them)
+        m, f = ema_momentum, ema_overwrite_frequency
+        if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0.0 <= m <= 1.0:
+            raise ValueError(f"ema_momentum must lie in [0, 1], got {m!r}")
+        if f is not None and (isinstance(f, bool) or not isinstance(f, int) or f < 1):
+            raise ValueError(f"ema_overwrite_frequency must be None or an integer >= 1, got {f!r}")
+        if f is not None and (k or 1) > 1 and f % k:
+            raise ValueError(f"ema_overwrite_frequency ({f}) must be a multiple of gradient_accumulation_steps ({k}): "
+                             "the average moves, and can overwrite, on apply micro-steps only")
+        self.use_ema, self.ema_momentum, self.ema_overwrite_frequency = bool(use_ema), float(m), f
+        self._ema_fresh = False  # build() allocated E and nothing has filled it yet (init_ema)
         self._lr = learning_rate
         self.clipnorm, self.clipvalue, self.global_clipnorm = clipnorm, clipvalue, global_clipnorm
         self.weight_decay = weight_decay
@@ -67,8 +94,7 @@ class Optimizer:
         # f64 partial sums; allocated before any graph capture
         self._clip_out: Optional[torch.Tensor] = None
         self._clip_partials: Optional[torch.Tensor] = None
-        unknown = set(kwargs) - {"decay", "amsgrad_legacy", "jit_compile", "is_legacy_optimizer",
-                                 "use_ema", "ema_momentum", "ema_overwrite_frequency"}
+        unknown = set(kwargs) - {"decay", "amsgrad_legacy", "jit_compile", "is_legacy_optimizer"}
         if unknown:
             raise TypeError(f"{type(self).__name__}: unexpected arguments {sorted(unknown)}")
 
@@ -109,13 +135,16 @@ class Optimizer:
 
     _update_zeroes_grad = False  # the device update kernel can zero G once it has read it (``zero_grad``)
 
-    def device_update(self, W: torch.Tensor, G: torch.Tensor, t_add: int = 0, zero_grad: bool = False) -> bool:
+    def device_update(self, W: torch.Tensor, G: torch.Tensor, t_add: int = 0, zero_grad: bool = False,
+                      phase_add: Optional[int] = None) -> bool:
         """One hand-written flat-slab update kernel (learning rate and step count read from the
         device: capturable) when this optimizer has one and the slab is on the GPU; False
         otherwise (the caller then uses apply_flat).  ``t_add``: the step's offset inside an
         execution whose first step is t_dev (Adam).  ``zero_grad``: the generic trainer's request to
         zero G after its use, so its next step needs no fill launch; only a kernel of an optimizer
-        with ``_update_zeroes_grad`` honours it, the others ignore it."""
+        with ``_update_zeroes_grad`` honours it, the others ignore it.  ``phase_add``: the step's offset from
+        ``iterations`` (the weight EMA's overwrite phase); ``t_add`` unless given -- ``apply_flat``, whose
+        callers advance ``iterations`` every step, passes 0."""
         return False
 
     def set_layout(self, layout):
@@ -140,7 +169,10 @@ class Optimizer:
 
             self._clip_out = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device)
             self._clip_partials = torch.zeros(max(1, ops.hip().clip_partials(n)), dtype=torch.float64, device=device)
-        for k in self._slot_names() + ([ACCUMULATOR] if self._accumulating else []):
+        if self.use_ema:
+            old = self._slots.get(EMA)
+            self._ema_fresh = old is None or old.numel() != n
+        for k in self._slot_names() + ([ACCUMULATOR] if self._accumulating else []) + ([EMA] if self.use_ema else []):
             old = self._slots.get(k)
             self._slots[k] = old.to(device) if (old is not None and old.numel() == n) else torch.zeros(
                 n, dtype=torch.float32, device=device)
@@ -238,21 +270,114 @@ class Optimizer:
             G.mul_(c)
         return mode == 2
 
+    # ------------------------------------------------------------------ weight EMA
+    def _ema_mode(self, t_add: int = 0) -> int:
+        """The EMA mode of the update ``t_add`` steps from now: 2 when its 1-based step count
+        ``iterations + t_add + 1`` is a multiple of ``ema_overwrite_frequency`` (update E, store W = E), else 1
+        (update E); 0 with ``use_ema`` off.  The host knows it at launch and at capture time."""
+        if not self.use_ema:
+            return 0
+        f = self.ema_overwrite_frequency
+        return 2 if f is not None and (int(self.iterations) + int(t_add) + 1) % f == 0 else 1
+
+    def init_ema(self, W: torch.Tensor):
+        """E = W once, for an ``E`` that ``build`` has just allocated (TF 2.11+'s ``initial_value=var``): the
+        engines call it after ``build`` and before any capture.  An ``E`` that ``load_state_dict`` brought, or
+        that has been filled before, is kept."""
+        if not self.use_ema:
+            return
+        if self._n != W.numel() or self._device != W.device:
+            self.build(W.numel(), W.device)
+        if self._ema_fresh:
+            with torch.no_grad():
+                self._slots[EMA].copy_(W)
+            self._ema_fresh = False
+
+    def device_ema(self, W: torch.Tensor, t_add: int = 0) -> dict:
+        """The EMA operands of this optimizer's update kernel over the GPU slab ``W`` for the step ``t_add``
+        from ``iterations`` (analogous to ``device_clip``): the kernel keeps ``E`` where it stores ``w``, at no
+        extra launch.  Empty with ``use_ema`` off, and for a slice of the slab (the fused engine's two buckets):
+        its caller runs ``ema_after`` over the whole slab once every bucket is updated."""
+        if not self.use_ema or W.numel() != self._n:
+            return {}
+        from .. import ops
+
+        if not hasattr(ops.hip(), "weight_ema"):
+            raise RuntimeError("use_ema: the extension has no weight_ema kernel for the GPU slab "
+                               "(rebuild: python build_native.py)")
+        self.init_ema(W)
+        return {"ema": self._slots[EMA], "ema_momentum": self.ema_momentum, "ema_mode": self._ema_mode(t_add)}
+
+    def ema_after(self, W: torch.Tensor, t_add: int = 0):
+        """``E = float32(m) * E + float32(1 - m) * W`` after an update of the whole slab ``W`` that no update
+        kernel of ours made (the step ``t_add`` from ``iterations``; on an overwrite step also ``W = E``): one
+        launch of ``_C.weight_ema`` on a GPU slab (capturable, the mode is baked in at capture), the torch form
+        of the numpy expression on the CPU.  A no-op with ``use_ema`` off."""
+        if not self.use_ema:
+            return
+        self.init_ema(W)
+        E, mode = self._slots[EMA], self._ema_mode(t_add)
+        if W.device.type == "cuda":
+            from .. import ops
+
+            if W.dtype != torch.float32 or not hasattr(ops.hip(), "weight_ema"):
+                raise RuntimeError("use_ema: the extension has no weight_ema kernel for the GPU slab "
+                                   "(rebuild: python build_native.py)")
+            ops.hip().weight_ema(W, E, self.ema_momentum, mode)
+            return
+        with torch.no_grad():
+            # two products and a sum, each rounded to f32 (no ``alpha=``: that form may fuse)
+            E.mul_(_f32(self.ema_momentum)).add_(W * _f32(1.0 - self.ema_momentum))
+            if mode == 2:
+                W.copy_(E)
+
+    def finalize_slab(self, W: torch.Tensor):
+        """``W = E`` over the whole slab (the end of ``fit``); a no-op with ``use_ema`` off."""
+        if self.use_ema and EMA in self._slots and self._slots[EMA].numel() == W.numel() and not self._ema_fresh:
+            with torch.no_grad():
+                W.copy_(self._slots[EMA].to(W.device))
+
+    def finalize_variable_values(self, var_list):
+        """Keras' ``finalize_variable_values`` for custom loops: every variable of ``var_list`` (the ones, in
+        the order, ``apply_gradients`` updated) is overwritten with its moving average.  A plain copy: not on
+        the hot path.  A no-op with ``use_ema`` off or before the first update."""
+        if not self.use_ema or EMA not in self._slots or self._ema_fresh:
+            return
+        E = self._slots[EMA]
+        var_list = list(var_list)
+        lay = self._layout
+        if lay is not None and lay.total == E.numel() and len(lay.layer_spans()[0]) == len(var_list):
+            views = list(lay.views(E))
+        else:
+            sizes = [int(math.prod(v.shape)) for v in var_list]
+            if sum(sizes) != E.numel():
+                raise ValueError(f"finalize_variable_values: the variables hold {sum(sizes)} elements, the moving "
+                                 f"average {E.numel()}")
+            views, off = [], 0
+            for n in sizes:
+                views.append(E[off:off + n])
+                off += n
+        for v, e in zip(var_list, views):
+            v.assign(e.reshape(v.shape))
+
     def apply_flat(self, W: torch.Tensor, G: torch.Tensor, sync_lr: bool = True, t_add: int = 0,
                    accumulated: bool = False, zero_grad: bool = False) -> bool:
         """w <- update(w, g) over the whole slab (gradients already all-reduced).  ``t_add``: this
         step's offset from ``t_dev`` inside a multi-step execution (only Adam reads a step count).
         With gradient accumulation on, ``G`` is first folded (``accumulate``) unless the caller has done so
         (``accumulated=True``); a micro-step that is not the cycle's last only counts.  Returns whether the
-        update kernel zeroed ``G`` after reading it, as ``zero_grad`` asked (see ``device_update``)."""
+        update kernel zeroed ``G`` after reading it, as ``zero_grad`` asked (see ``device_update``).  With
+        ``use_ema`` the moving average follows the update: inside the update kernel, else by ``ema_after``."""
         if self._n != W.numel() or self._device != W.device:
             self.build(W.numel(), W.device)
+        self.init_ema(W)
         if self._accumulating and not accumulated and not self.accumulate(G):
             self.iterations += 1
             return False
         if sync_lr:
             self._sync_lr()
-        if self.device_update(W, G, t_add, zero_grad=zero_grad):  # clip + (decay +) update in the kernel
+        # clip + (decay +) update (+ moving average) in the kernel; (``iterations`` is this step's: phase_add 0)
+        if self.device_update(W, G, t_add, zero_grad=zero_grad, phase_add=0):
             self.iterations += 1
             return bool(zero_grad) and self._update_zeroes_grad
         self._clip(G)
@@ -260,6 +385,7 @@ class Optimizer:
             W.mul_(1.0 - self.current_lr() * self.weight_decay)
         with torch.no_grad():
             self._update(W, G)
+        self.ema_after(W)  # (no update kernel ran: an _update that retries device_update fails as it did above)
         self.iterations += 1
         return False
 
@@ -327,7 +453,8 @@ class Optimizer:
             lr = _sched.serialize(lr)
         return {"name": self.name, "learning_rate": lr, "clipnorm": self.clipnorm, "clipvalue": self.clipvalue,
                 "global_clipnorm": self.global_clipnorm,
-                "gradient_accumulation_steps": self.gradient_accumulation_steps}
+                "gradient_accumulation_steps": self.gradient_accumulation_steps, "use_ema": self.use_ema,
+                "ema_momentum": self.ema_momentum, "ema_overwrite_frequency": self.ema_overwrite_frequency}
 
     @classmethod
     def from_config(cls, cfg):
@@ -343,9 +470,12 @@ class Optimizer:
         self.iterations = int(st.get("iterations", 0))
         for k, v in st.get("slots", {}).items():
             self._slots[k] = v.to(self._device) if self._device is not None else v.clone()
+            if k == EMA:
+                self._ema_fresh = False  # (a restored average is kept: init_ema leaves it alone)
 
 
 ACCUMULATOR = "gradient_accumulator"  # the slot of the f32 accumulator slab
+EMA = "ema"  # the slot of the f32 moving average of the weights
 
 
 def _kernel_present(kernel: str) -> bool:
@@ -382,18 +512,18 @@ class SGD(Optimizer):
     def _slot_names(self):
         return ["momentum"] if self.momentum > 0 else []
 
-    def device_update(self, W, G, t_add=0, zero_grad=False):
+    def device_update(self, W, G, t_add=0, zero_grad=False, phase_add=None):
         if not _hip_ok(W, "sgd", self) or self.weight_decay:
             return False
         from .. import ops
 
         C = ops.hip()
-        clip = self.device_clip(G)
+        extra = dict(self.device_clip(G), **self.device_ema(W, t_add if phase_add is None else phase_add))
         if self.momentum > 0:
             C.sgd_momentum(W, G, self._slots["momentum"], self.lr_dev, self.momentum, self.nesterov,
-                           zero_grad=bool(zero_grad), **clip)
+                           zero_grad=bool(zero_grad), **extra)
         else:
-            C.sgd(W, G, self.lr_dev, zero_grad=bool(zero_grad), **clip)
+            C.sgd(W, G, self.lr_dev, zero_grad=bool(zero_grad), **extra)
         return True
 
     def _update(self, W, G):
@@ -432,7 +562,7 @@ class Adam(Optimizer):
 
     _needs_step = True
 
-    def device_update(self, W, G, t_add=0, zero_grad=False):
+    def device_update(self, W, G, t_add=0, zero_grad=False, phase_add=None):
         """csrc/kernels/optim.hip k_adam (AdamW's decoupled decay inside the same pass)."""
         if not _hip_ok(W, "adam", self):
             return False
@@ -440,7 +570,7 @@ class Adam(Optimizer):
 
         ops.hip().adam(W, G, self._slots["m"], self._slots["v"], self._slots.get("vhat"), self.lr_dev, self.t_dev,
                        int(t_add), self.beta_1, self.beta_2, self.epsilon, float(self.weight_decay or 0.0),
-                       **self.device_clip(G))
+                       **self.device_clip(G), **self.device_ema(W, t_add if phase_add is None else phase_add))
         return True
 
     def _update(self, W, G):
@@ -478,14 +608,15 @@ class RMSprop(Optimizer):
     # (the torch fallback bakes lr; clipping: see Adam.graph_safe)
     graph_safe = property(lambda self: self._clip_on_device and _kernel_present("rmsprop"))
 
-    def device_update(self, W, G, t_add=0, zero_grad=False):
+    def device_update(self, W, G, t_add=0, zero_grad=False, phase_add=None):
         """csrc/kernels/optim.hip k_rmsprop."""
         if not _hip_ok(W, "rmsprop", self) or self.weight_decay:
             return False
         from .. import ops
 
         ops.hip().rmsprop(W, G, self._slots["rms"], self._slots.get("mom"), self._slots.get("mg"), self.lr_dev,
-                          self.rho, self.momentum, self.epsilon, **self.device_clip(G))
+                          self.rho, self.momentum, self.epsilon, **self.device_clip(G),
+                          **self.device_ema(W, t_add if phase_add is None else phase_add))
         return True
 
     def _update(self, W, G):
@@ -524,13 +655,14 @@ class Adagrad(Optimizer):
 
     graph_safe = property(lambda self: self._clip_on_device and _kernel_present("adagrad"))
 
-    def device_update(self, W, G, t_add=0, zero_grad=False):
+    def device_update(self, W, G, t_add=0, zero_grad=False, phase_add=None):
         """csrc/kernels/optim.hip k_adagrad."""
         if not _hip_ok(W, "adagrad", self) or self.weight_decay:
             return False
         from .. import ops
 
-        ops.hip().adagrad(W, G, self._slots["acc"], self.lr_dev, self.epsilon, **self.device_clip(G))
+        ops.hip().adagrad(W, G, self._slots["acc"], self.lr_dev, self.epsilon, **self.device_clip(G),
+                          **self.device_ema(W, t_add if phase_add is None else phase_add))
         return True
 
     def _update(self, W, G):
@@ -625,8 +757,8 @@ class _Layerwise(Optimizer):
         (see Adam.graph_safe)."""
         return self._tables is not None and self._clip_on_device
 
-    def device_update(self, W, G, t_add=0, zero_grad=False):
-        """csrc/kernels/layerwise.hip: chunk sums, per-variable ratios, update."""
+    def device_update(self, W, G, t_add=0, zero_grad=False, phase_add=None):
+        """csrc/kernels/layerwise.hip: chunk sums, per-variable ratios, update (the moving average in it)."""
         if W.device.type != "cuda" or W.dtype != torch.float32:
             return False
         if self._tables is None or not self._clip_on_device:
@@ -636,10 +768,11 @@ class _Layerwise(Optimizer):
             raise RuntimeError(f"{type(self).__name__} updates the whole slab ({self._n} elements), got {W.numel()}")
         from .. import ops
 
-        self._launch(ops.hip(), W, G, int(t_add), self.device_clip(G))
+        self._launch(ops.hip(), W, G, int(t_add), self.device_clip(G),
+                     self.device_ema(W, t_add if phase_add is None else phase_add))
         return True
 
-    def _launch(self, C, W, G, t_add, clip):
+    def _launch(self, C, W, G, t_add, clip, ema):
         raise NotImplementedError
 
     def _views(self, *flats):
@@ -699,12 +832,12 @@ class LARS(_Layerwise):
     def _slot_names(self):
         return ["momentum"]
 
-    def _launch(self, C, W, G, t_add, clip):
+    def _launch(self, C, W, G, t_add, clip, ema):
         T = self._tables
         C.lars_sums(T, W, G, self._layer_partials, **clip)
         C.lars_ratio(T, self._layer_partials, self._layer_ratio, self._layer_norms, self.eeta, self.epsilon)
         C.lars_update(T, W, G, self._slots["momentum"], self._layer_ratio, self.lr_dev, self.momentum, self.nesterov,
-                      **clip)
+                      **clip, **ema)
 
     def _update(self, W, G):
         lr, mu = _f32(self.current_lr()), self.momentum
@@ -756,12 +889,12 @@ class LAMB(_Layerwise):
     def _slot_names(self):
         return ["m", "v"]
 
-    def _launch(self, C, W, G, t_add, clip):
+    def _launch(self, C, W, G, t_add, clip, ema):
         T, m, v = self._tables, self._slots["m"], self._slots["v"]
         hp = (self.t_dev, t_add, self.beta_1, self.beta_2, self.epsilon)
         C.lamb_sums(T, W, G, m, v, self._layer_partials, *hp, **clip)
         C.lamb_ratio(T, self._layer_partials, self._layer_ratio, self._layer_norms)
-        C.lamb_update(T, W, m, v, self._layer_ratio, self.lr_dev, *hp)
+        C.lamb_update(T, W, m, v, self._layer_ratio, self.lr_dev, *hp, **ema)
 
     def _update(self, W, G):
         lr = _f32(self.current_lr())
