@@ -11,6 +11,7 @@
 #include "kernels/dropout.h"
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
+#include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
 #include "kernels/stem.h"
@@ -50,6 +51,40 @@ std::vector<at::Tensor> gather_xy(at::Tensor X, at::Tensor Y, at::Tensor idx) {
   tdl::gather_xy(X.data_ptr<float>(), Y.data_ptr(), idx.data_ptr<int>(), x.data_ptr<float>(), y.data_ptr(), rows,
                  row_elems, (int)Y.element_size(), cur_stream());
   return {x, y};
+}
+
+// gather_xy with a third, f32 column W [N] (sample weights): (x, y, w) = (X[idx], Y[idx], W[idx]) in one launch.
+// out_x / out_y / out_w: optional preallocated outputs (tests put guard words around them)
+std::vector<at::Tensor> gather_xyw(at::Tensor X, at::Tensor Y, at::Tensor W, at::Tensor idx,
+                                   c10::optional<at::Tensor> out_x, c10::optional<at::Tensor> out_y,
+                                   c10::optional<at::Tensor> out_w) {
+  TORCH_CHECK(X.is_cuda() && Y.is_cuda() && W.is_cuda() && idx.is_cuda(), "gather_xyw: GPU tensors expected");
+  TORCH_CHECK(X.is_contiguous() && Y.is_contiguous() && W.is_contiguous() && idx.is_contiguous(),
+              "gather_xyw: contiguous tensors expected");
+  TORCH_CHECK(X.scalar_type() == at::kFloat && X.dim() >= 1, "gather_xyw: X must be f32 [N, ...]");
+  TORCH_CHECK((Y.scalar_type() == at::kLong || Y.scalar_type() == at::kInt) && Y.dim() == 1 && Y.size(0) == X.size(0),
+              "gather_xyw: Y must be int64 / int32 [N]");
+  TORCH_CHECK(W.scalar_type() == at::kFloat && W.dim() == 1 && W.size(0) == X.size(0), "gather_xyw: W must be f32 [N]");
+  TORCH_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 1, "gather_xyw: idx must be int32 [n]");
+  const int64_t rows = idx.numel();
+  auto shape = X.sizes().vec();
+  shape[0] = rows;
+  const int64_t row_elems = X.size(0) > 0 ? X.numel() / X.size(0) : 0;
+  auto given = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
+  auto x = given(out_x) ? *out_x : at::empty(shape, X.options());
+  auto y = given(out_y) ? *out_y : at::empty({rows}, Y.options());
+  auto w = given(out_w) ? *out_w : at::empty({rows}, W.options());
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.scalar_type() == at::kFloat && x.numel() == rows * row_elems,
+              "gather_xyw: out_x must be f32 with ", rows * row_elems, " elements");
+  TORCH_CHECK(y.is_cuda() && y.is_contiguous() && y.scalar_type() == Y.scalar_type() && y.numel() == rows,
+              "gather_xyw: out_y must have Y's dtype and ", rows, " elements");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && w.scalar_type() == at::kFloat && w.numel() == rows,
+              "gather_xyw: out_w must be f32 with ", rows, " elements");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "gather_xyw: X and out_x must be 16-byte aligned");
+  tdl::gather_xyw(X.data_ptr<float>(), Y.data_ptr(), W.data_ptr<float>(), idx.data_ptr<int>(), x.data_ptr<float>(),
+                  y.data_ptr(), w.data_ptr<float>(), rows, row_elems, (int)Y.element_size(), cur_stream());
+  return {x, y, w};
 }
 
 tdl::BnDType bn_dtype(const at::Tensor& x) {
@@ -1278,6 +1313,58 @@ std::vector<at::Tensor> xent_head(at::Tensor z, at::Tensor labels, double gn, c1
   return {loss, dz};
 }
 
+const float* f32_vec(const c10::optional<at::Tensor>& t, int64_t n, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->dim() == 1 && t->size(0) == n,
+              what, ": f32 GPU vector of ", n, " elements expected");
+  return t->data_ptr<float>();
+}
+
+// xent_head with sample weights sw [N], class weights cw [K], label smoothing eps, and sparse (int64 [N]) or
+// dense (f32 [N][K]) targets (kernels/loss_head.h).  dz_out / rows_ws: optional preallocated dz and row
+// workspace ([3N] f32, used above 64K logits); tests put guard words around them
+std::vector<at::Tensor> xent_head_w(at::Tensor z, at::Tensor target, double gn, c10::optional<at::Tensor> sw,
+                                    c10::optional<at::Tensor> cw, double eps, c10::optional<at::Tensor> lt_total,
+                                    c10::optional<at::Tensor> lt_count, c10::optional<at::Tensor> acc_total,
+                                    c10::optional<at::Tensor> acc_count, c10::optional<at::Tensor> dz_out,
+                                    c10::optional<at::Tensor> rows_ws) {
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == at::kFloat && z.dim() == 2 && z.size(1) >= 1,
+              "xent_head_w: f32 [N][K >= 1] logits");
+  TORCH_CHECK(target.is_cuda() && target.is_contiguous(), "xent_head_w: contiguous GPU target");
+  const bool dense = target.scalar_type() == at::kFloat;
+  if (dense) {
+    TORCH_CHECK(target.sizes() == z.sizes(), "xent_head_w: dense f32 targets must have the logits' shape");
+  } else {
+    TORCH_CHECK(target.scalar_type() == at::kLong && target.dim() == 1 && target.size(0) == z.size(0),
+                "xent_head_w: int64 [N] labels or f32 [N][K] targets");
+  }
+  TORCH_CHECK(gn > 0, "xent_head_w: global batch must be positive");
+  TORCH_CHECK(eps >= 0.0 && eps <= 1.0, "xent_head_w: label smoothing must be in [0, 1]");
+  const int64_t N = z.size(0), K = z.size(1);
+  TORCH_CHECK(z.numel() < (int64_t(1) << 31), "xent_head_w: too many logits");
+  const float* swp = f32_vec(sw, N, "xent_head_w sw");
+  const float* cwp = f32_vec(cw, K, "xent_head_w cw");
+  auto loss = at::empty({}, z.options());
+  auto given = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->defined(); };
+  auto dz = given(dz_out) ? *dz_out : fresh(z.sizes(), z.options());
+  TORCH_CHECK(dz.is_cuda() && dz.is_contiguous() && dz.scalar_type() == at::kFloat && dz.numel() == z.numel(),
+              "xent_head_w: dz_out must be f32 with the logits' element count");
+  // the form switches where xent_head's does: one workgroup up to 64K logits, else rows + finish
+  at::Tensor ws;
+  if (z.numel() > 65536) {
+    ws = given(rows_ws) ? *rows_ws : at::empty({3 * N}, z.options());
+    TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() && ws.scalar_type() == at::kFloat && ws.numel() >= 3 * N,
+                "xent_head_w: rows_ws must be f32 with at least 3 N elements");
+  }
+  tdl::xent_head_w(z.data_ptr<float>(),
+                   dense ? nullptr : reinterpret_cast<const long long*>(target.data_ptr<int64_t>()),
+                   dense ? target.data_ptr<float>() : nullptr, swp, cwp, (int)N, (int)K, gn, (float)eps,
+                   loss.data_ptr<float>(), dz.data_ptr<float>(), f64_scalar(lt_total, "lt_total"),
+                   f64_scalar(lt_count, "lt_count"), f64_scalar(acc_total, "acc_total"),
+                   f64_scalar(acc_count, "acc_count"), ws.defined() ? ws.data_ptr<float>() : nullptr, cur_stream());
+  return {loss, dz};
+}
+
 at::Tensor xent_bwd(at::Tensor z, at::Tensor labels, at::Tensor g) {
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() && z.scalar_type() == at::kFloat && z.dim() == 2, "xent: f32 [N][K] logits");
   TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.scalar_type() == at::kLong &&
@@ -1297,6 +1384,12 @@ void register_ops(pybind11::module& m) {
         "the loss / accuracy metric accumulators", pybind11::arg("z"), pybind11::arg("labels"), pybind11::arg("gn"),
         pybind11::arg("lt_total") = pybind11::none(), pybind11::arg("lt_count") = pybind11::none(),
         pybind11::arg("acc_total") = pybind11::none(), pybind11::arg("acc_count") = pybind11::none());
+  m.def("xent_head_w", &xent_head_w, "fused loss head with sample weights, class weights, label smoothing and "
+        "sparse or dense targets", pybind11::arg("z"), pybind11::arg("target"), pybind11::arg("gn"),
+        pybind11::arg("sw") = pybind11::none(), pybind11::arg("cw") = pybind11::none(), pybind11::arg("eps") = 0.0,
+        pybind11::arg("lt_total") = pybind11::none(), pybind11::arg("lt_count") = pybind11::none(),
+        pybind11::arg("acc_total") = pybind11::none(), pybind11::arg("acc_count") = pybind11::none(),
+        pybind11::arg("dz_out") = pybind11::none(), pybind11::arg("rows_ws") = pybind11::none());
   m.def("gemm_bf16", &gemm_bf16, "bf16 MFMA GEMM with either storage per operand (Dense fwd / dgrad / wgrad)",
         pybind11::arg("a"), pybind11::arg("ta"), pybind11::arg("b"), pybind11::arg("tb"),
         pybind11::arg("bias") = pybind11::none(), pybind11::arg("out") = pybind11::none(),
@@ -1428,6 +1521,10 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("h"), pybind11::arg("wd"), pybind11::arg("pt"),
         pybind11::arg("pl"), pybind11::arg("residual") = pybind11::none());
   m.def("gather_xy", &gather_xy, "a batch of (feature row, label) pairs of a device-resident dataset, one launch");
+  m.def("gather_xyw", &gather_xyw, "a batch of (feature row, label, f32 weight) triples of a device-resident "
+        "dataset, one launch", pybind11::arg("X"), pybind11::arg("Y"), pybind11::arg("W"), pybind11::arg("idx"),
+        pybind11::arg("out_x") = pybind11::none(), pybind11::arg("out_y") = pybind11::none(),
+        pybind11::arg("out_w") = pybind11::none());
   m.def("bn_forward_train", &bn_forward_train, "NHWC batch-norm training forward (+relu)", pybind11::arg("x"),
         pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("moving_mean"), pybind11::arg("moving_var"),
         pybind11::arg("momentum"), pybind11::arg("eps"), pybind11::arg("relu") = false,

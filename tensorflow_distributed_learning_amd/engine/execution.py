@@ -81,6 +81,23 @@ def accum_key(opt, key: tuple, t_add: int = 0) -> tuple:
     return key + (opt._accum_phase(t_add),) if opt._accumulating else key
 
 
+def weights_tag(sample_w: bool, class_w: bool) -> tuple:
+    """Graph-key element of a step whose loss head reads a sample-weight column and / or the class-weight
+    table: which of the two are present picks the head's kernel variant, which a capture bakes in.  Keys of
+    unweighted steps carry no such element (they are what they were)."""
+    return ("weights", bool(sample_w), bool(class_w))
+
+
+def weights_key(key: tuple, sample_w: bool, class_w: bool) -> tuple:
+    """``key`` of an execution graph, with the weights tag when the execution is weighted (it goes in front of
+    the accumulation / EMA phase that ``accum_key`` appends)."""
+    return key + (weights_tag(sample_w, class_w),) if sample_w or class_w else key
+
+
+def has_class_weight(key: tuple) -> bool:
+    return any(isinstance(e, tuple) and len(e) == 3 and e[0] == "weights" and e[2] for e in key)
+
+
 def phase_period(opt, K: int = 1) -> int:
     """How many distinct starting phases the K-step executions of a run can have (the ``accum_steps``
     of ``execution_starts``): the accumulation steps, or, with EMA overwrites on, the number of

@@ -85,6 +85,8 @@ def eligible(model, dataset=None) -> Optional[str]:
     if not (isinstance(lo, losses.SparseCategoricalCrossentropy) and lo.from_logits and lo.ignore_class is None and
             lo.reduction in (losses.Reduction.AUTO, losses.Reduction.SUM_OVER_BATCH_SIZE)):
         return "loss is not SparseCategoricalCrossentropy(from_logits=True)"
+    if lo.label_smoothing:
+        return "label smoothing is not in the fused step's loss head"
     opt = model.optimizer
     if type(opt) not in (optimizers.SGD, optimizers.Adam, optimizers.AdamW, optimizers.RMSprop, optimizers.Adagrad,
                          optimizers.LARS, optimizers.LAMB):
@@ -205,6 +207,11 @@ class FusedMnistTrainer(EX.Prefetching):
         return self._capture_comm
 
     # ------------------------------------------------------------------ data
+    def set_class_weight(self, table):
+        """The fused step's loss head is unweighted: Model.fit trains a weighted fit on the generic engine."""
+        if table is not None:
+            raise RuntimeError("the fused MNIST engine has no class weights (Model.fit uses the generic engine)")
+
     def prepare(self, dataset):
         lp = DD.lower(dataset)
         cols = _reference_columns(lp)

@@ -180,6 +180,10 @@ class MirroredFusedTrainer(EX.Prefetching):
         """The all-reduce is recorded inside every device's execution graph."""
         return self.mode in ("xchg", "xgmi") and self.capture
 
+    def set_class_weight(self, table):
+        for s in self.subs:
+            s.set_class_weight(table)
+
     def broadcast_from_primary(self):
         """Replica 0's weights and optimizer state onto every replica (mirrored variables)."""
         s0 = self.subs[0]
@@ -644,6 +648,10 @@ class ThreadedGroupTrainer:
             if t.model._NT is not None and t0.model._NT is not None:
                 t.model._NT.copy_(t0.model._NT.to(t.model._NT.device))
             _copy_optimizer_state(t.optimizer, t0.optimizer)
+
+    def set_class_weight(self, table):
+        """fit(class_weight=...): every replica's trainer keeps its own device copy of the table."""
+        self.group.run(lambda r: self.trainers[r].set_class_weight(table))
 
     def prepare(self, dataset):
         return None  # no device-resident path: host pipeline (host_handler)

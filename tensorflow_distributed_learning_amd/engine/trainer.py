@@ -173,6 +173,12 @@ class GenericTrainer:
         # device-resident executions (prepare()): the uploaded dataset's identity, the execution's index
         # buffer and the pinned ring it is filled through, the batch size and the sizes that have run eagerly
         self._dev_key = self._dev_idx = self._dev_b = None
+        self._SW = None  # (the uploaded dataset's f32 sample-weight column, when it has one)
+        # fit(class_weight=...): ONE persistent f32 [K] table on the device, updated in place by a later fit (a
+        # captured graph keeps reading it); whether it is in use picks the loss head's kernel variant, so it
+        # is part of every graph key
+        self._cw: Optional[torch.Tensor] = None
+        self._cw_on = False
         self._dev_ring = EX.IndexRing(self.device, 4)
         self._dev_warm = set()
         # metric accumulators start from zero for callers that drive run_train() directly
@@ -370,6 +376,25 @@ class GenericTrainer:
         for i, leaf in enumerate(self._leaves):
             leaf.register_post_accumulate_grad_hook(hook_for(i))
 
+    # ------------------------------------------------------------------ class weights
+    def set_class_weight(self, table: Optional[torch.Tensor]):
+        """The f32 [K] class-weight table of this fit (``Model._class_weight_table``), or None for a fit without."""
+        if table is None:
+            self._cw_on = False
+            return
+        if self._cw is None or self._cw.shape != table.shape:
+            self._cw = torch.empty(table.shape, dtype=torch.float32, device=self.device)
+            self._graphs = {k: v for k, v in self._graphs.items() if not EX.has_class_weight(k)}  # (the old table)
+        self._cw.copy_(table.to(torch.float32))
+        self._cw_on = True
+
+    def _row_weight(self, y, sw, cw):
+        """``sw * cw[class]`` with torch (the path without the fused head): the class of a row is its label, or
+        the argmax of a dense target."""
+        cls = y.argmax(-1) if y.is_floating_point() and y.dim() > 1 else y.reshape(-1).long()
+        w = cw[cls]
+        return w if sw is None else sw.to(w.dtype).reshape(-1) * w
+
     # ------------------------------------------------------------------ steps
     def _forward_loss(self, x, y, sw, global_n):
         model = self.model
@@ -382,13 +407,16 @@ class GenericTrainer:
 
         with ctx, _training_replica(self.strategy.extended.rank):
             y_pred = model(x, training=True)
-        fused = self._fused_head(y, y_pred, sw)
+        cw = self._cw if self._cw_on else None
+        fused = self._fused_head(y, y_pred, sw, cw)
         if fused is not None:
             loss = fused(global_n)
             reg = model._regularization_loss()
             if reg is not None:
                 loss = loss + reg / self.strategy.num_replicas_in_sync
-            return loss, None, y_pred
+            return loss, None, y_pred, sw
+        if cw is not None:
+            sw = self._row_weight(y, sw, cw)
         per_ex = self.loss.per_example(y, y_pred.float() if y_pred.dtype != torch.float32 else y_pred)
         if sw is not None:
             per_ex = per_ex * sw.to(per_ex.dtype)
@@ -397,7 +425,7 @@ class GenericTrainer:
         reg = model._regularization_loss()
         if reg is not None:
             loss = loss + reg / self.strategy.num_replicas_in_sync
-        return loss, per_ex, y_pred
+        return loss, per_ex, y_pred, sw
 
     def _seed(self) -> torch.Tensor:
         """The backward seed d(loss)/d(loss) = 1, allocated once (autograd would fill a new one every
@@ -407,25 +435,48 @@ class GenericTrainer:
             s = self._seed_t = torch.ones((), dtype=torch.float32, device=self.device)
         return s
 
-    def _fused_head(self, y, y_pred, sw):
-        """The one-kernel loss head (ops/dense.py xent_head) when the step's loss and metrics are what it
-        computes: SparseCategoricalCrossentropy(from_logits=True) on f32 2-D logits, no sample weights,
-        metrics none or SparseCategoricalAccuracy.  Returns ``f(global_n) -> loss`` (the metric
-        accumulators are advanced by the kernel), or None."""
+    def _fused_head(self, y, y_pred, sw, cw=None):
+        """The one-kernel loss head when the step's loss and metrics are what it computes, on f32 2-D logits:
+
+        * ops/dense.py ``xent_head``: SparseCategoricalCrossentropy(from_logits=True) without smoothing, sample
+          or class weights, metrics none or SparseCategoricalAccuracy;
+        * ops/dense.py ``xent_head_w``: the same loss with label smoothing, sample weights ``sw`` or the class
+          weight table ``cw``; or CategoricalCrossentropy(from_logits=True) on dense targets, with or without
+          any of those, metrics none or CategoricalAccuracy.
+
+        Returns ``f(global_n) -> loss`` (the metric accumulators are advanced by the kernel), or None."""
         from ..keras import losses as _losses
         from ..keras import metrics as _metrics
         from ..ops import dense as _dense
 
-        if (sw is not None or y is None or os.environ.get("TDL_FUSED_HEAD", "1") != "1" or
-                not isinstance(self.loss, _losses.SparseCategoricalCrossentropy) or not self.loss.from_logits or
-                self.loss.ignore_class is not None or y_pred.dim() != 2 or y.dim() != 1 or
-                y_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16)):
+        if (y is None or os.environ.get("TDL_FUSED_HEAD", "1") != "1" or not getattr(self.loss, "from_logits", False) or
+                y_pred.dim() != 2 or y_pred.dtype not in (torch.float32, torch.bfloat16, torch.float16)):
             return None
+        if type(self.loss) is _losses.CategoricalCrossentropy:
+            dense, metric = True, _metrics.CategoricalAccuracy
+            if y.shape != y_pred.shape or not y.is_floating_point():
+                return None
+        elif isinstance(self.loss, _losses.SparseCategoricalCrossentropy) and self.loss.ignore_class is None:
+            dense, metric = False, _metrics.SparseCategoricalAccuracy
+            if y.dim() != 1:
+                return None
+        else:
+            return None
+        if len(self.metrics) > 1 or (self.metrics and type(self.metrics[0]) is not metric):
+            return None
+        eps = float(getattr(self.loss, "label_smoothing", 0.0) or 0.0)
+        weighted = dense or eps != 0.0 or sw is not None or cw is not None
         # (mixed precision: the loss is computed on f32 logits, as the unfused path's y_pred.float())
         y_pred = y_pred.float() if y_pred.dtype != torch.float32 else y_pred
-        if not _dense.xent_head_supported(y_pred, y.long()):
-            return None
-        if len(self.metrics) > 1 or (self.metrics and type(self.metrics[0]) is not _metrics.SparseCategoricalAccuracy):
+        target = y.float() if dense else y.long()
+        if weighted:
+            if sw is not None:
+                if sw.dim() != 1 or not sw.is_floating_point():
+                    return None
+                sw = sw.float()
+            if not _dense.xent_head_w_supported(y_pred, target, sw, cw):
+                return None
+        elif not _dense.xent_head_supported(y_pred, target):
             return None
         accs = []
         for m in [self.loss_tracker] + list(self.metrics):
@@ -433,8 +484,9 @@ class GenericTrainer:
             accs += [m.total._value, m.count._value]
         while len(accs) < 4:
             accs.append(None)
-        labels = y.long()
-        return lambda gn: _dense.xent_head(y_pred, labels, gn, accs[:2], accs[2:], seed=self._seed())
+        if not weighted:
+            return lambda gn: _dense.xent_head(y_pred, target, gn, accs[:2], accs[2:], seed=self._seed())
+        return lambda gn: _dense.xent_head_w(y_pred, target, gn, sw, cw, eps, accs[:2], accs[2:], seed=self._seed())
 
     def train_step(self, batch, global_n: int, sync_lr: bool = True, t_add: int = 0):
         """One whole step.  ``t_add``: the step's offset inside a multi-step execution graph whose
@@ -466,7 +518,8 @@ class GenericTrainer:
         torch.backends.cudnn.benchmark = search_prev or self._conv_search
         try:
             with trace_range("tdl.forward"):
-                loss, per_ex, y_pred = self._forward_loss(x, y, sw, global_n)
+                # (sw: from here on the row weight, sample weight x class weight, the metrics get as well)
+                loss, per_ex, y_pred, sw = self._forward_loss(x, y, sw, global_n)
         except BaseException:
             torch.backends.cudnn.benchmark = search_prev
             raise
@@ -587,6 +640,8 @@ class GenericTrainer:
             key += (("accum", self._accum_mode()),)
         if self.optimizer.use_ema:  # so is the step's EMA mode (update E / also overwrite W)
             key += (("ema", self.optimizer._ema_mode()),)
+        if self._cw_on:  # and the loss head's kernel variant (a sample-weight column is in the batch signature)
+            key += (EX.weights_tag(False, True),)
         ent = self._graphs.get(key)
         if ent is None:
             seen = self._seen.get(key, 0) + 1
@@ -629,8 +684,9 @@ class GenericTrainer:
     # ------------------------------------------------------------------ device-resident executions
     def prepare(self, dataset):
         """Device-resident input for ANY model (the fused engine's data path, data/device.py): an
-        in-memory ``[map].cache().shuffle().batch().repeat()`` pipeline of (features, labels) is
-        uploaded to HBM once, and each execution of ``steps_per_execution`` steps is ONE captured
+        in-memory ``[map].cache().shuffle().batch().repeat()`` pipeline of (features, labels) or
+        (features, labels, sample weights: a 1-D float column, kept as f32) is uploaded to HBM once,
+        and each execution of ``steps_per_execution`` steps is ONE captured
         hipGraph that gathers its batches from HBM by the execution's index vector (one async H2D
         copy per execution) and runs K whole steps: forward, backward, all-reduce, optimizer and
         metrics (TF's ``steps_per_execution``: K steps per ``tf.function`` call).  None: host pipeline.
@@ -640,24 +696,33 @@ class GenericTrainer:
         from ..data import device as DD
 
         lp = DD.lower(dataset)
-        if lp is None or not isinstance(lp.columns, (tuple, list)) or len(lp.columns) != 2:
+        if lp is None or not isinstance(lp.columns, (tuple, list)) or len(lp.columns) not in (2, 3):
             return None
-        x, y = lp.columns
+        x, y = lp.columns[:2]
+        sw = lp.columns[2] if len(lp.columns) == 3 else None
         if not (isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor)) or not x.is_floating_point():
+            return None
+        if len(lp.columns) == 3 and not (isinstance(sw, torch.Tensor) and sw.dim() == 1 and sw.is_floating_point()
+                                         and sw.shape[0] == x.shape[0]):
             return None
         R = self.comm.world_size
         if lp.batch_size % R or not self._graphable():  # (_graphable is collective at R > 1: every rank is here)
             return None
         key = (x.data_ptr(), tuple(x.shape), y.data_ptr(), tuple(y.shape), x._version, y._version)
+        if sw is not None:
+            key += (sw.data_ptr(), sw._version)
         if self._dev_key != key:
             self._X = x.to(self.device).contiguous()
             self._Y = y.to(self.device).contiguous()
+            self._SW = sw.to(self.device, torch.float32).contiguous() if sw is not None else None
             self._dev_key = key
+            self._graphs = {k: v for k, v in self._graphs.items() if k[0] != "dev"}  # they read the old columns
         from ..ops import hip
 
         self._gather_xy = (self._X.dtype == torch.float32 and self._Y.dim() == 1 and
                            self._Y.dtype in (torch.int64, torch.int32) and hasattr(hip(), "gather_xy") and
-                           self._X.data_ptr() % 16 == 0)
+                           self._X.data_ptr() % 16 == 0 and
+                           (self._SW is None or hasattr(hip(), "gather_xyw")))
         policy = input_lib.effective_policy(dataset) if R > 1 else None
         seed = input_lib.shared_seed(self.strategy) if policy is not None and policy.name in ("DATA", "FILE") else None
         return EX.DeviceHandler(lp, seed, self.comm.rank, R)
@@ -674,13 +739,19 @@ class GenericTrainer:
 
     def _dev_step(self, k: int, b: int, global_n: int, sync_lr: bool):
         ii = self._dev_idx[k * b:(k + 1) * b]
-        if self._gather_xy:  # features and labels of the batch in one hand-written kernel
+        if self._gather_xy:  # the batch's features and labels (and weights) in one hand-written kernel
             from ..ops import hip
 
-            x, y = hip().gather_xy(self._X, self._Y, ii)
+            batch = tuple(hip().gather_xy(self._X, self._Y, ii) if self._SW is None else
+                          hip().gather_xyw(self._X, self._Y, self._SW, ii))
         else:
-            x, y = self._X.index_select(0, ii), self._Y.index_select(0, ii)
-        self.train_step((x, y), global_n, sync_lr=sync_lr, t_add=k)
+            batch = tuple(c.index_select(0, ii) for c in (self._X, self._Y, self._SW) if c is not None)
+        self.train_step(batch, global_n, sync_lr=sync_lr, t_add=k)
+
+    def _dev_graph_key(self, K: int, b: int) -> tuple:
+        """Base key of the K-step execution graph at batch size b; a weighted execution's carries which weights
+        its loss head reads (``accum_key`` appends the accumulation / EMA phase)."""
+        return EX.weights_key(("dev", K, b), self._SW is not None, self._cw_on)
 
     def warm_graphs(self, steps: int, b: Optional[int] = None):
         """Capture (without running) the execution graphs ``run_train(steps)`` will replay, once a
@@ -696,7 +767,7 @@ class GenericTrainer:
         if self._dev_idx is None or self._dev_idx.numel() < n:
             self._dev_upload(np.zeros(n, dtype=np.int32))
         for k, t_add in starts:
-            if EX.accum_key(opt, ("dev", k, b), t_add) not in self._graphs:
+            if EX.accum_key(opt, self._dev_graph_key(k, b), t_add) not in self._graphs:
                 self._dev_capture(k, b, t_add)
 
     def _run_device(self, handler, steps: int) -> int:
@@ -723,7 +794,7 @@ class GenericTrainer:
             K = idx.size // b
             self._dev_upload(idx)
             opt._sync_lr()
-            graph = self._graphs.get(EX.accum_key(opt, ("dev", K, b)))
+            graph = self._graphs.get(EX.accum_key(opt, self._dev_graph_key(K, b)))
             if (graph is None and b in self._dev_warm and self._graph_ok is not False and
                     os.environ.get("TDL_GENERIC_DEVICE_EAGER", "0") != "1"):
                 graph = self._dev_capture(K, b)
@@ -744,7 +815,7 @@ class GenericTrainer:
     def _dev_capture(self, K: int, b: int, t_add: int = 0):
         """Capture the K-step execution that starts ``t_add`` micro-steps from now (only its accumulation
         phase depends on the start: the step count the kernels read is on the device)."""
-        key = EX.accum_key(self.optimizer, ("dev", K, b), t_add)
+        key = EX.accum_key(self.optimizer, self._dev_graph_key(K, b), t_add)
         try:
             with EX.capturing(self.device, self.optimizer, t_add) as graph:
                 for k in range(K):

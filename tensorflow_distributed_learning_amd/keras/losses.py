@@ -46,13 +46,16 @@ def _snake(n):
 
 
 class SparseCategoricalCrossentropy(Loss):
-    """Integer labels; ``from_logits=True`` fuses log-softmax + NLL (tf_dist_example.py:50)."""
+    """Integer labels; ``from_logits=True`` fuses log-softmax + NLL (tf_dist_example.py:50).
+    ``label_smoothing`` is an extension (Keras has it on CategoricalCrossentropy only): the target of a row is
+    ``(1 - eps) onehot + eps / K``, as ``F.cross_entropy(label_smoothing=eps)``."""
 
     def __init__(self, from_logits=False, ignore_class=None, reduction=Reduction.AUTO,
-                 name="sparse_categorical_crossentropy"):
+                 name="sparse_categorical_crossentropy", label_smoothing=0.0):
         super().__init__(reduction, name)
         self.from_logits = from_logits
         self.ignore_class = ignore_class
+        self.label_smoothing = float(label_smoothing)
 
     def per_example(self, y_true, y_pred):
         y = y_true.reshape(-1).long() if y_true.dim() > 1 and y_true.shape[-1] == 1 else y_true.long()
@@ -61,18 +64,19 @@ class SparseCategoricalCrossentropy(Loss):
         if logits.dim() > 2:
             logits = logits.reshape(-1, logits.shape[-1])
             y = y.reshape(-1)
-        if self.from_logits and self.ignore_class is None:
+        if self.from_logits and self.ignore_class is None and not self.label_smoothing:
             from ..ops import dense as _dense
 
             if _dense.xent_supported(logits, y):
                 return _dense.softmax_xent(logits, y)  # hand-written kernel (csrc/kernels/gemm.hip)
-        l = F.cross_entropy(logits, y, reduction="none")
+        l = F.cross_entropy(logits, y, reduction="none", label_smoothing=self.label_smoothing)
         if self.ignore_class is not None:
             l = l * (y != self.ignore_class)
         return l
 
     def get_config(self):
-        return dict(super().get_config(), from_logits=self.from_logits)
+        return dict(super().get_config(), from_logits=self.from_logits, label_smoothing=self.label_smoothing,
+                    ignore_class=self.ignore_class)
 
 
 class CategoricalCrossentropy(Loss):
@@ -88,6 +92,11 @@ class CategoricalCrossentropy(Loss):
         logp = torch.log_softmax(y_pred, -1) if self.from_logits else torch.log(
             (y_pred / y_pred.sum(-1, keepdim=True)).clamp_min(1e-7))
         return -(y * logp).sum(-1)
+
+    def get_config(self):
+        # (ignore_class: this loss has none; the key is there so that both cross-entropies carry the same three)
+        return dict(super().get_config(), from_logits=self.from_logits, label_smoothing=self.label_smoothing,
+                    ignore_class=None)
 
 
 class BinaryCrossentropy(Loss):

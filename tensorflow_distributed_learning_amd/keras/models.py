@@ -303,7 +303,13 @@ class Model(Layer):
             ms = metrics or []
             if isinstance(ms, dict):
                 ms = [m for v in ms.values() for m in (v if isinstance(v, list) else [v])]
-            self.compiled_metrics = [_metrics.get(m, self.loss) for m in ms]
+            # weighted_metrics: appended to the compiled metrics.  EVERY compiled metric receives the step's row
+            # weight (sample weight x class weight) here, also those given as metrics= (Keras leaves those
+            # unweighted; README, "Weighted and smoothed loss head")
+            wms = weighted_metrics or []
+            if isinstance(wms, dict):
+                wms = [m for v in wms.values() for m in (v if isinstance(v, list) else [v])]
+            self.compiled_metrics = [_metrics.get(m, self.loss) for m in list(ms) + list(wms)]
             self._loss_tracker = _metrics.Mean(name="loss")
         self._steps_per_execution = int(steps_per_execution or 1)
         # RCCL all-reduce bucket size for overlap with backward (0 = one all-reduce per step,
@@ -325,8 +331,10 @@ class Model(Layer):
         if cfg.get("loss"):
             loss = _losses.get(cfg["loss"])
             for k, v in (cfg.get("loss_config") or {}).items():
-                if k == "from_logits":
-                    loss.from_logits = v
+                if k in ("from_logits", "ignore_class") and hasattr(loss, k):
+                    setattr(loss, k, v)
+                elif k == "label_smoothing" and hasattr(loss, k):
+                    loss.label_smoothing = float(v or 0.0)
         self.compile(optimizer=_opt.get(cfg["optimizer"]), loss=loss, metrics=cfg.get("metrics") or None,
                      steps_per_execution=cfg.get("steps_per_execution", 1))
 
@@ -482,8 +490,23 @@ class Model(Layer):
             x, y = x[:cut], y[:cut]
         ds = self._adapt(x, y, batch_size, shuffle, sample_weight)
         self._peek_build(ds)
+        cw_table = self._class_weight_table(class_weight)
         trainer = self._get_trainer()
         group = getattr(trainer, "is_group", False)
+        if trainer.kind == "fused" and (cw_table is not None or _has_weight_column(ds)):
+            # the fused MNIST step's loss head has no weights: the generic engine (its weighted loss head, device-
+            # resident input and execution graphs) trains this fit
+            if group:
+                from ..engine.mirrored import ThreadedGroupTrainer, _models_and_group
+
+                self._trainer = trainer = ThreadedGroupTrainer(self, *_models_and_group(self))
+            else:
+                from ..engine.trainer import GenericTrainer
+
+                self._trainer = trainer = GenericTrainer(self)
+            self._fused_reason = ("class_weight" if cw_table is not None else "sample weights") + \
+                ": the fused step's loss head is unweighted"
+        trainer.set_class_weight(cw_table)
         if group:
             trainer.broadcast_from_primary()  # weights / optimizer state set since the last fit
         handler = trainer.prepare(ds) if hasattr(trainer, "prepare") else None
@@ -499,6 +522,7 @@ class Model(Layer):
 
                     self._trainer = trainer = GenericTrainer(self)
                 self._fused_reason = "input pipeline is not device-resident"
+                trainer.set_class_weight(cw_table)
             if hasattr(trainer, "host_handler"):
                 handler = trainer.host_handler(ds)
             else:
@@ -596,6 +620,29 @@ class Model(Layer):
         cb_list.on_train_end(logs)
         self.history = history
         return history
+
+    def _class_weight_table(self, class_weight):
+        """``fit(class_weight={class: weight})`` as an f32 [K] table, K the model's output width; a class that
+        is not named weighs 1.  None without class weights."""
+        if class_weight is None:
+            return None
+        if not isinstance(class_weight, dict):
+            raise ValueError(f"class_weight must be a dict {{class: weight}}, got {type(class_weight).__name__}")
+        if self._functional:
+            shape = self._outputs.shape if isinstance(self._outputs, KerasTensor) else None
+        else:
+            shape = getattr(self, "_output_shape", None)  # (Sequential: set when its layers are built)
+        K = shape[-1] if isinstance(shape, (tuple, list)) and len(shape) >= 2 else None
+        if not isinstance(K, int) or isinstance(K, bool) or K < 1:
+            raise ValueError("class_weight needs a Sequential or functional model with one output of known width")
+        table = torch.ones(K, dtype=torch.float32)
+        for c, w in class_weight.items():
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)):
+                raise ValueError(f"class_weight key {c!r} is not an integer class index")
+            if c < 0 or c >= K:
+                raise ValueError(f"class_weight key {c} is outside the model's classes [0, {K})")
+            table[int(c)] = float(w)
+        return table
 
     def _check_replicas(self, trainer):
         """Collective: the mirrored parameters must be bit-identical on every replica
@@ -845,6 +892,15 @@ class _LazyLogs:
         from ..engine.trainer import LazyLogs
 
         return LazyLogs(trainer.logs)
+
+
+def _has_weight_column(ds) -> bool:
+    """Whether the pipeline, lowered to in-memory columns (what the fused engine trains from; a pipeline that
+    does not lower leaves that engine anyway), has a third, sample-weight column."""
+    from ..data import device as DD
+
+    lp = DD.lower(ds)
+    return lp is not None and isinstance(lp.columns, (tuple, list)) and len(lp.columns) >= 3
 
 
 def _lowered_steps(handler):

@@ -8,6 +8,9 @@ GlobalAveragePooling2D, Dense and sparse softmax cross-entropy for bf16 activati
   With gradient-slab targets (``Variable.grad_target``) dW and db are ADDED into the f32 slab.
 * ``softmax_xent``: per-example ``logsumexp(z) - z[label]`` on f32 logits, backward
   ``(softmax - onehot) * g`` in one pass.
+* ``xent_head`` / ``xent_head_w``: the generic engine's whole loss head in one kernel (mean-reduced loss, its
+  logit gradient, the metric accumulators); ``xent_head_w`` (csrc/kernels/loss_head.hip) adds sample weights,
+  class weights, label smoothing and dense targets.
 
 Reference: the Keras layers / loss of ``tf_dist_example.py:41-50`` (and keras.applications.ResNet50).
 """
@@ -144,3 +147,52 @@ def xent_head(z: torch.Tensor, labels: torch.Tensor, global_n: int, loss_acc=(No
     accumulators ``(total, count)`` advanced in place -- instead of ~15 PyTorch reduction / elementwise
     kernels per step (tf_dist_example.py:49-52)."""
     return _XentHead.apply(z, labels, float(global_n), tuple(loss_acc) + tuple(acc_acc), seed)
+
+
+class _XentHeadW(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, target, gn, sw, cw, eps, accs, seed):
+        loss, dz = hip().xent_head_w(z.contiguous(), target.contiguous(), float(gn), sw, cw, float(eps), *accs)
+        ctx.save_for_backward(dz)
+        ctx.seed_ptr = seed.data_ptr() if seed is not None else None
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        if ctx.seed_ptr is not None and g.data_ptr() == ctx.seed_ptr:
+            return (dz,) + (None,) * 7  # the trainer's own backward seed (1.0): no scaling kernel
+        return (dz * g,) + (None,) * 7
+
+
+def xent_head_w_supported(z: torch.Tensor, target: torch.Tensor, sw: Optional[torch.Tensor] = None,
+                          cw: Optional[torch.Tensor] = None) -> bool:
+    """f32 [N, K] logits with int64 [N] labels or f32 [N, K] targets; ``sw`` f32 [N] and ``cw`` f32 [K] on the
+    logits' device when given."""
+    if not (z.is_cuda and z.dtype == torch.float32 and z.dim() == 2 and z.shape[0] >= 1 and z.shape[1] >= 1 and
+            z.numel() < 2 ** 31 and target.device == z.device):
+        return False
+    if target.dtype == torch.float32:
+        if target.shape != z.shape:
+            return False
+    elif target.dtype != torch.int64 or target.dim() != 1 or target.shape[0] != z.shape[0]:
+        return False
+    for t, n in ((sw, z.shape[0]), (cw, z.shape[1])):
+        if t is not None and not (t.device == z.device and t.dtype == torch.float32 and t.dim() == 1 and
+                                  t.shape[0] == n):
+            return False
+    return hasattr(hip(), "xent_head_w")
+
+
+def xent_head_w(z: torch.Tensor, target: torch.Tensor, global_n: int, sample_weight: Optional[torch.Tensor] = None,
+                class_weight: Optional[torch.Tensor] = None, label_smoothing: float = 0.0, loss_acc=(None, None),
+                acc_acc=(None, None), seed: Optional[torch.Tensor] = None):
+    """``xent_head`` with per-row weights ``sample_weight[r] * class_weight[class]``, label smoothing and sparse
+    (int64 [N]) or dense (f32 [N, K], one-hot or soft) targets, still ONE kernel (csrc/kernels/loss_head.hip):
+    ``sum(w * per-example loss) / global_n``, its logit gradient (saved for the backward), and the f64
+    accumulators of the loss tracker ``(+= sum w loss, += N)`` and of the (Sparse)CategoricalAccuracy
+    ``(+= sum w correct, += sum w)``.  Without weights and smoothing, sparse labels give ``xent_head``'s bits."""
+    sw = sample_weight.contiguous() if sample_weight is not None else None
+    cw = class_weight.contiguous() if class_weight is not None else None
+    return _XentHeadW.apply(z, target, float(global_n), sw, cw, float(label_smoothing),
+                            tuple(loss_acc) + tuple(acc_acc), seed)
