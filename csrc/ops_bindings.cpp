@@ -8,6 +8,7 @@
 
 #include "kernels/bn.h"
 #include "kernels/conv.h"
+#include "kernels/augment.h"
 #include "kernels/dropout.h"
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
@@ -503,6 +504,93 @@ at::Tensor dropout_bwd(at::Tensor dy, at::Tensor ticket, int64_t k0, int64_t k1,
                   ticket.device() == dy.device(),
               "dropout: ticket must be the forward's 1-element int64 tensor");
   return dropout_run(dy, nullptr, ticket.data_ptr<int64_t>(), nullptr, k0, k1, T, scale, noise_strides, elem_offset);
+}
+
+// ---- seeded image augmentation (csrc/kernels/augment.hip; the draws, the map and the fill modes: kernels/augment.h) ----
+// spec = (flip_h, flip_w, off_h_lo, off_h_count, off_w_lo, off_w_count, out_h, out_w, fill_mode, fill_value):
+// the offsets are drawn from [lo, lo + count), fill_mode is 0 constant, 1 nearest, 2 wrap, 3 reflect
+tdl::AugmentArgs augment_args(const at::Tensor& src, int64_t H, int64_t W, int64_t k0, int64_t k1, bool flip_h,
+                              bool flip_w, int64_t off_h_lo, int64_t off_h_count, int64_t off_w_lo,
+                              int64_t off_w_count, int64_t out_h, int64_t out_w, int64_t fill_mode,
+                              double fill_value) {
+  TORCH_CHECK(src.is_cuda() && src.is_contiguous() && src.dim() == 4, "augment: contiguous NHWC GPU tensor expected");
+  TORCH_CHECK(src.scalar_type() == at::kFloat || src.scalar_type() == at::kBFloat16,
+              "augment: float32 or bfloat16 expected");
+  TORCH_CHECK(k0 >= 0 && k0 <= 0xffffffffLL && k1 >= 0 && k1 <= 0xffffffffLL, "augment: key words are 32-bit");
+  TORCH_CHECK(fill_mode >= 0 && fill_mode <= 3,
+              "augment: fill_mode must be 0 (constant), 1 (nearest), 2 (wrap) or 3 (reflect)");
+  const int64_t lim = (1LL << 31) - 1;
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= lim && W <= lim && src.size(3) >= 1 && src.size(3) <= lim / 4 && src.size(0) <= lim,
+              "augment: sizes out of range");
+  TORCH_CHECK(out_h >= 1 && out_h <= H && out_w >= 1 && out_w <= W, "augment: the output must be no larger than the input");
+  TORCH_CHECK(off_h_count >= 1 && off_w_count >= 1, "augment: an offset range needs at least one value");
+  TORCH_CHECK(off_h_lo >= -H && off_h_lo + off_h_count - 1 <= H && off_w_lo >= -W && off_w_lo + off_w_count - 1 <= W,
+              "augment: offsets must stay within [-size, size]");
+  const bool bf16 = src.scalar_type() == at::kBFloat16;
+  tdl::AugmentArgs a;
+  a.src = src.data_ptr();
+  a.dst = nullptr;
+  a.N = src.size(0);
+  a.H = (int)H;
+  a.W = (int)W;
+  a.Ho = (int)out_h;
+  a.Wo = (int)out_w;
+  a.C = (int)src.size(3);
+  a.state = nullptr;
+  a.ticket_in = nullptr;
+  a.ticket_out = nullptr;
+  a.k0 = (uint32_t)k0;
+  a.k1 = (uint32_t)k1;
+  a.spec.flip_h = flip_h;
+  a.spec.flip_w = flip_w;
+  a.spec.off_h_lo = (int)off_h_lo;
+  a.spec.off_h_count = (int)off_h_count;
+  a.spec.off_w_lo = (int)off_w_lo;
+  a.spec.off_w_count = (int)off_w_count;
+  a.spec.fill_mode = (int)fill_mode;
+  // the fill value rounded ONCE to the tensor's dtype (bf16: to nearest even), as bits
+  if (bf16) {
+    a.spec.fill_bits = (uint32_t)c10::BFloat16((float)fill_value).x;
+  } else {
+    const float f = (float)fill_value;
+    memcpy(&a.spec.fill_bits, &f, 4);
+  }
+  a.bf16 = bf16;
+  return a;
+}
+
+std::vector<at::Tensor> augment_fwd(at::Tensor x, at::Tensor state, int64_t k0, int64_t k1, bool flip_h, bool flip_w,
+                                    int64_t off_h_lo, int64_t off_h_count, int64_t off_w_lo, int64_t off_w_count,
+                                    int64_t out_h, int64_t out_w, int64_t fill_mode, double fill_value) {
+  TORCH_CHECK(x.dim() == 4, "augment: NHWC tensor expected");
+  auto a = augment_args(x, x.size(1), x.size(2), k0, k1, flip_h, flip_w, off_h_lo, off_h_count, off_w_lo, off_w_count,
+                        out_h, out_w, fill_mode, fill_value);
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.numel() == 2 && state.is_contiguous() &&
+                  state.device() == x.device(),
+              "augment: state must be an int64 [calls, arrivals] tensor on x's device");
+  auto ticket = at::empty({1}, state.options());
+  auto y = at::empty({x.size(0), out_h, out_w, x.size(3)}, x.options());
+  a.dst = y.data_ptr();
+  a.state = state.data_ptr<int64_t>();
+  a.ticket_out = ticket.data_ptr<int64_t>();
+  tdl::augment_forward(a, cur_stream());
+  return {y, ticket};
+}
+
+at::Tensor augment_bwd(at::Tensor dy, at::Tensor ticket, int64_t k0, int64_t k1, bool flip_h, bool flip_w,
+                       int64_t off_h_lo, int64_t off_h_count, int64_t off_w_lo, int64_t off_w_count, int64_t out_h,
+                       int64_t out_w, int64_t fill_mode, double fill_value, int64_t H, int64_t W) {
+  auto a = augment_args(dy, H, W, k0, k1, flip_h, flip_w, off_h_lo, off_h_count, off_w_lo, off_w_count, out_h, out_w,
+                        fill_mode, fill_value);
+  TORCH_CHECK(dy.size(1) == out_h && dy.size(2) == out_w, "augment: dy must be [N, out_h, out_w, C]");
+  TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kLong && ticket.numel() == 1 &&
+                  ticket.device() == dy.device(),
+              "augment: ticket must be the forward's 1-element int64 tensor");
+  auto dx = at::empty({dy.size(0), H, W, dy.size(3)}, dy.options());
+  a.dst = dx.data_ptr();
+  a.ticket_in = ticket.data_ptr<int64_t>();
+  tdl::augment_backward(a, cur_stream());
+  return dx;
 }
 
 // backward of maxpool_fwd(bn_stats=...): (dz, part) -- dz the BN -> ReLU group's masked input gradient,
@@ -1489,6 +1577,21 @@ void register_ops(pybind11::module& m) {
   m.def("conv_wgrad3x3_set_rows", &tdl::conv_wgrad3x3_set_rows, "3x3 row-kernel wgrad: output rows per slice (0 = auto)");
   m.def("conv_wgrad_force_single", &tdl::conv_wgrad_force_single,
         "weight-gradient A/B hook: single LDS stage at 3 waves/SIMD (True) or double-buffered (False, default)");
+  m.attr("AUGMENT_WG_ELEMS") = (int64_t)tdl::kAugmentWgElems;  // work items (16-B vectors / elements) per workgroup and trip
+  m.attr("AUGMENT_MAX_GRID") = (int64_t)tdl::kAugmentMaxGrid;  // grid cap of the augmentation kernels
+  m.attr("AUGMENT_FWD_MAX_GRID") = (int64_t)tdl::kAugmentFwdMaxGrid;  // ... of the forward (it arrives at the counter)
+  m.def("augment_force_max_grid", &tdl::augment_force_max_grid,
+        "augment test hook: grid cap (0 = AUGMENT_FWD_MAX_GRID / AUGMENT_MAX_GRID)");
+  m.def("augment_fwd", &augment_fwd,
+        "seeded flip / crop / translation forward: (y, ticket); advances state = [calls, arrivals]", py::arg("x"),
+        py::arg("state"), py::arg("k0"), py::arg("k1"), py::arg("flip_h"), py::arg("flip_w"), py::arg("off_h_lo"),
+        py::arg("off_h_count"), py::arg("off_w_lo"), py::arg("off_w_count"), py::arg("out_h"), py::arg("out_w"),
+        py::arg("fill_mode") = 0, py::arg("fill_value") = 0.0);
+  m.def("augment_bwd", &augment_bwd,
+        "seeded flip / crop / translation backward: dx [N, H, W, C] from dy and the forward's ticket (draws recomputed)",
+        py::arg("dy"), py::arg("ticket"), py::arg("k0"), py::arg("k1"), py::arg("flip_h"), py::arg("flip_w"),
+        py::arg("off_h_lo"), py::arg("off_h_count"), py::arg("off_w_lo"), py::arg("off_w_count"), py::arg("out_h"),
+        py::arg("out_w"), py::arg("fill_mode"), py::arg("fill_value"), py::arg("H"), py::arg("W"));
   m.attr("DROPOUT_WG_ELEMS") = (int64_t)tdl::kDropoutWgElems;  // elements per workgroup and grid-stride trip
   m.attr("DROPOUT_MAX_GRID") = (int64_t)tdl::kDropoutMaxGrid;  // grid cap of the dropout kernels
   m.attr("DROPOUT_SMALL_N") = (int64_t)tdl::kDropoutSmallN;    // up to this many elements: ...

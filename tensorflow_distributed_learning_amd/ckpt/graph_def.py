@@ -13,7 +13,7 @@
 * the inference computation of every layer, NHWC, float32 -- Conv2D (+BiasAdd), Dense (MatMul +
   BiasAdd), Max/AvgPool, Mean/Max (global pools), Reshape (Flatten/Reshape), Pad (ZeroPadding2D),
   FusedBatchNormV3 (``is_training=false``: moving statistics), AddV2/AddN/Sub/Mul/Maximum/ConcatV2
-  (merge layers), the activations, Identity for Dropout;
+  (merge layers), the activations, Identity for Dropout, RandomFlip and RandomTranslation;
 * the outputs as ``StatefulPartitionedCall`` (Identity, or IdentityN for several outputs), the names
   the signature has always used;
 * a V2 ``Saver``: ``save/Const`` (PlaceholderWithDefault filename), ``SaveV2`` / ``RestoreV2`` over
@@ -403,6 +403,8 @@ def _emit_layer(g: _Graph, layer, sc: str, xs: List[str], in_shape, read) -> str
         return g.add(f"{sc}/Softmax", "Softmax", [x], T=T)
     if isinstance(layer, L.Dropout):
         return g.add(f"{sc}/Identity", "Identity", [x], T=T)  # inference: no dropout
+    if isinstance(layer, (L.RandomFlip, L.RandomTranslation)):
+        return g.add(f"{sc}/Identity", "Identity", [x], T=T)  # inference: no augmentation
     if isinstance(layer, L.Rescaling):
         y = g.add(f"{sc}/mul", "Mul", [x, g.const_f32(f"{sc}/Cast", float(layer.scale))], T=T)
         return g.add(f"{sc}/add", "AddV2", [y, g.const_f32(f"{sc}/Cast_1", float(layer.offset))], T=T)

@@ -331,8 +331,9 @@ class GenericTrainer:
         comm.prepare_all_reduce(*self._sync_bn_sizes)
 
     def _prepare_dropout(self):
-        """Dropout layers keep their call counter in a device tensor that the forward kernel advances
-        (ops/dropout.py): create it now, so that a captured step records no allocation or fill of it."""
+        """Dropout and the random image layers keep their call counter in a device tensor that the forward
+        kernel advances (ops/dropout.py, ops/augment.py): create it now, so that a captured step records no
+        allocation or fill of it."""
         if self.device.type != "cuda":
             return
         from ..keras import layers as L
@@ -343,7 +344,7 @@ class GenericTrainer:
                 yield from walk(l)
 
         for l in walk(self.model):
-            if isinstance(l, L.Dropout):
+            if isinstance(l, L._CallCounterRNG):
                 l._state_for(self.device)
 
     def _register_bucket_hooks(self):

@@ -690,7 +690,68 @@ def _replica_id() -> int:
     return int(_st.get_strategy().extended.rank)
 
 
-class Dropout(Layer):
+class _CallCounterRNG:
+    """Mix-in of the layers that draw from the Philox stream of ops/dropout.py (Dropout, the random image
+    layers): the seed and stream rules, the per-replica key, and the call counter -- a ``[calls, arrivals]``
+    tensor per device that the forward kernel advances, a Python counter on the CPU.
+
+    An explicit seed uses stream 0, so two layers with one seed draw alike; ``None`` uses the global seed
+    (``keras.utils.set_random_seed``; unset: ``torch.initial_seed()`` at first use) and the layer's creation
+    index as its stream (``backend.clear_session`` restarts the index)."""
+
+    def _init_rng(self, seed):
+        self.seed = None if seed is None else int(seed)
+        if self.seed is None:
+            self._rng_stream = _DROPOUT_STREAMS[0]
+            _DROPOUT_STREAMS[0] += 1
+        else:
+            self._rng_stream = 0
+        self._rng_state: Dict[torch.device, torch.Tensor] = {}
+        self._cpu_calls = 0
+
+    def _key(self):
+        from ..ops import dropout as _do
+
+        seed = self.seed if self.seed is not None else _do.global_seed()
+        return _do.stream_key(seed, self._rng_stream, _replica_id())
+
+    def _state_for(self, device) -> torch.Tensor:
+        """The device's ``[calls, arrivals]`` tensor, created on first use (outside any graph capture: the
+        engines create it before they capture a step)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._rng_state.get(device)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self.name}: the layer's call counter of {device} must exist before a graph "
+                                   "capture (call the layer once eagerly, or layer._state_for(device))")
+            st = self._rng_state[device] = torch.zeros(2, dtype=torch.int64, device=device)
+        return st
+
+    def _take_cpu_ticket(self) -> int:
+        t = self._cpu_calls
+        self._cpu_calls += 1
+        return t
+
+    def reset_rng(self, calls: int = 0):
+        """Restart the call counter at ``calls`` on every device (and on the CPU): the draws replay."""
+        self._cpu_calls = int(calls)
+        for st in self._rng_state.values():
+            st.copy_(torch.tensor([int(calls), 0], dtype=torch.int64))
+
+    def rng_calls(self, device="cpu") -> int:
+        """Calls counted on ``device`` so far (synchronises; for tests and debugging)."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            return self._cpu_calls
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        st = self._rng_state.get(device)
+        return 0 if st is None else int(st.cpu()[0])
+
+
+class Dropout(_CallCounterRNG, Layer):
     """tf.keras.layers.Dropout with a reproducible mask (ops/dropout.py): the mask of a call is a function
     of (seed, the layer's stream, the replica, the call number) alone, the same bits on the CPU and on the
     GPU, in eager steps and in replayed graphs, and it is recomputed in the backward instead of saved.
@@ -716,51 +777,7 @@ class Dropout(Layer):
             if any(d is not None and d < 1 for d in noise_shape):
                 raise ValueError(f"{type(self).__name__}: noise_shape entries must be None or positive, got {noise_shape}")
         self.noise_shape = noise_shape
-        self.seed = None if seed is None else int(seed)
-        if self.seed is None:
-            self._rng_stream = _DROPOUT_STREAMS[0]
-            _DROPOUT_STREAMS[0] += 1
-        else:
-            self._rng_stream = 0
-        self._rng_state: Dict[torch.device, torch.Tensor] = {}
-        self._cpu_calls = 0
-
-    # ------------------------------------------------------------------ RNG state
-    def _key(self):
-        from ..ops import dropout as _do
-
-        seed = self.seed if self.seed is not None else _do.global_seed()
-        return _do.stream_key(seed, self._rng_stream, _replica_id())
-
-    def _state_for(self, device) -> torch.Tensor:
-        """The device's ``[calls, arrivals]`` tensor, created on first use (outside any graph capture: the
-        engines create it before they capture a step)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        st = self._rng_state.get(device)
-        if st is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"{self.name}: the dropout call counter of {device} must exist before a graph "
-                                   "capture (call the layer once eagerly, or layer._state_for(device))")
-            st = self._rng_state[device] = torch.zeros(2, dtype=torch.int64, device=device)
-        return st
-
-    def reset_rng(self, calls: int = 0):
-        """Restart the call counter at ``calls`` on every device (and on the CPU): the masks replay."""
-        self._cpu_calls = int(calls)
-        for st in self._rng_state.values():
-            st.copy_(torch.tensor([int(calls), 0], dtype=torch.int64))
-
-    def rng_calls(self, device="cpu") -> int:
-        """Calls counted on ``device`` so far (synchronises; for tests and debugging)."""
-        device = torch.device(device)
-        if device.type != "cuda":
-            return self._cpu_calls
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        st = self._rng_state.get(device)
-        return 0 if st is None else int(st.cpu()[0])
+        self._init_rng(seed)
 
     # ------------------------------------------------------------------ call
     def _noise_shape_for(self, x):
@@ -792,9 +809,7 @@ class Dropout(Layer):
         ns = self._noise_shape_for(x)
         if x.is_cuda:
             return _do.dropout(x, self.rate, self._key(), state=self._state_for(x.device), noise_shape=ns)
-        t = self._cpu_calls
-        self._cpu_calls += 1
-        return _do.dropout(x, self.rate, self._key(), ticket=t, noise_shape=ns)
+        return _do.dropout(x, self.rate, self._key(), ticket=self._take_cpu_ticket(), noise_shape=ns)
 
     def compute_output_shape(self, s):
         return s
@@ -821,6 +836,149 @@ class SpatialDropout2D(Dropout):
         cfg = super().get_config()
         cfg.pop("noise_shape", None)
         return cfg
+
+
+class _RandomImageLayer(_CallCounterRNG, Layer):
+    """Base of the random image layers (ops/augment.py): in training one seeded coordinate transform per
+    sample of an NHWC batch, one kernel per direction on the GPU and inside the captured step; at inference
+    the identity (RandomCrop: the centre crop).  Seed, stream and replica rules are Dropout's, and so is the
+    call counter kept per device."""
+
+    def __init__(self, seed=None, **kw):
+        super().__init__(**kw)
+        self._init_rng(seed)
+
+    def _spec(self, H: int, W: int):
+        raise NotImplementedError
+
+    def _inference(self, x):
+        return x
+
+    def call(self, x, training=None):
+        from ..ops import augment as _au
+
+        if x.dim() != 4:
+            raise ValueError(f"{self.name}: a 4-D NHWC input is expected, got {x.dim()} dimensions")
+        spec = self._spec(int(x.shape[1]), int(x.shape[2]))
+        if not training:
+            return self._inference(x)
+        if x.is_cuda:
+            return _au.augment(x, spec, self._key(), state=self._state_for(x.device))
+        return _au.augment(x, spec, self._key(), ticket=self._take_cpu_ticket())
+
+    def compute_output_shape(self, s):
+        return s
+
+
+class RandomFlip(_RandomImageLayer):
+    """tf.keras.layers.RandomFlip (NHWC): in training each sample is flipped left-right (``"horizontal"``),
+    up-down (``"vertical"``) or both independently (``"horizontal_and_vertical"``) with probability 1/2."""
+
+    MODES = ("horizontal_and_vertical", "horizontal", "vertical")
+
+    def __init__(self, mode="horizontal_and_vertical", seed=None, **kw):
+        if mode not in self.MODES:
+            raise ValueError(f"RandomFlip: mode must be one of {self.MODES}, got {mode!r}")
+        super().__init__(seed=seed, **kw)
+        self.mode = mode
+
+    def _spec(self, H, W):
+        from ..ops.augment import Spec
+
+        return Spec(flip_h="vertical" in self.mode, flip_w="horizontal" in self.mode, out_h=H, out_w=W)
+
+    def get_config(self):
+        return dict(super().get_config(), mode=self.mode, seed=self.seed)
+
+
+class RandomCrop(_RandomImageLayer):
+    """tf.keras.layers.RandomCrop (NHWC): in training a ``height x width`` window at a uniformly drawn
+    position per sample; at inference the centre window (``top = (H - height) // 2``).  An input smaller
+    than the window raises ``ValueError`` (Keras resizes the image in that case; this layer does not)."""
+
+    def __init__(self, height, width, seed=None, **kw):
+        if int(height) != height or int(width) != width or height < 1 or width < 1:
+            raise ValueError(f"RandomCrop: height and width must be positive integers, got {height!r} x {width!r}")
+        super().__init__(seed=seed, **kw)
+        self.height, self.width = int(height), int(width)
+
+    def _spec(self, H, W):
+        from ..ops.augment import Spec
+
+        if H < self.height or W < self.width:
+            raise ValueError(f"{self.name}: the input {H} x {W} is smaller than the crop {self.height} x {self.width} "
+                             "(no resizing is done)")
+        return Spec(off_h_count=H - self.height + 1, off_w_count=W - self.width + 1, out_h=self.height,
+                    out_w=self.width)
+
+    def _inference(self, x):
+        top, left = (x.shape[1] - self.height) // 2, (x.shape[2] - self.width) // 2
+        return x[:, top:top + self.height, left:left + self.width, :]
+
+    def compute_output_shape(self, s):
+        return (s[0], self.height, self.width, s[3])
+
+    def get_config(self):
+        return dict(super().get_config(), height=self.height, width=self.width, seed=self.seed)
+
+
+def _factor_range(factor, what) -> Tuple[float, float]:
+    if isinstance(factor, (list, tuple)):
+        if len(factor) != 2:
+            raise ValueError(f"RandomTranslation: {what} must be a number or a pair, got {factor!r}")
+        a, b = float(factor[0]), float(factor[1])
+    else:
+        f = float(factor)
+        if not f >= 0.0:
+            raise ValueError(f"RandomTranslation: a scalar {what} must be non-negative, got {factor!r}")
+        a, b = -f, f
+    if not (-1.0 <= a <= b <= 1.0):  # (a NaN fails here too)
+        raise ValueError(f"RandomTranslation: {what} must be an ordered range within [-1, 1], got {factor!r}")
+    return a, b
+
+
+class RandomTranslation(_RandomImageLayer):
+    """tf.keras.layers.RandomTranslation (NHWC) in WHOLE pixels: in training each sample is shifted by ``d_h``
+    rows and ``d_w`` columns (positive = down / right, ``out[o] = in[o - d]``), drawn uniformly from the
+    integers of ``[ceil(a H), floor(b H)]`` where a factor is a scalar ``f`` (``a, b = -f, f``) or a pair
+    ``(a, b)``; that range must hold an integer and lie within ``[-H, H]``.  Pixels from outside the image
+    follow ``fill_mode``: ``"constant"`` (``fill_value``), ``"nearest"``, ``"wrap"`` or ``"reflect"``.
+
+    Keras draws fractional shifts and interpolates; here shifts are whole pixels, so ``interpolation``
+    ``"bilinear"`` and ``"nearest"`` are both accepted and mean the same, and the draws are not Keras' for any
+    seed (parity is unpinned)."""
+
+    def __init__(self, height_factor, width_factor, fill_mode="reflect", interpolation="bilinear", seed=None,
+                 fill_value=0.0, **kw):
+        from ..ops.augment import FILL_MODES
+
+        self._h_range = _factor_range(height_factor, "height_factor")
+        self._w_range = _factor_range(width_factor, "width_factor")
+        if fill_mode not in FILL_MODES:
+            raise ValueError(f"RandomTranslation: fill_mode must be one of {FILL_MODES}, got {fill_mode!r}")
+        if interpolation not in ("bilinear", "nearest"):
+            raise ValueError(f"RandomTranslation: interpolation must be 'bilinear' or 'nearest', got {interpolation!r}")
+        super().__init__(seed=seed, **kw)
+        self.height_factor, self.width_factor = height_factor, width_factor
+        self.fill_mode, self.interpolation, self.fill_value = fill_mode, interpolation, float(fill_value)
+
+    def _pixels(self, rng, size, what):
+        lo, hi = math.ceil(rng[0] * size), math.floor(rng[1] * size)
+        if lo > hi:
+            raise ValueError(f"{self.name}: {what} {rng} holds no whole-pixel shift of a size of {size}")
+        return -hi, hi - lo + 1  # a shift d reads in[o - d]: off = -d
+
+    def _spec(self, H, W):
+        from ..ops.augment import Spec
+
+        (hl, hc), (wl, wc) = self._pixels(self._h_range, H, "height_factor"), self._pixels(self._w_range, W, "width_factor")
+        return Spec(off_h_lo=hl, off_h_count=hc, off_w_lo=wl, off_w_count=wc, out_h=H, out_w=W,
+                    fill_mode=self.fill_mode, fill_value=self.fill_value)
+
+    def get_config(self):
+        as_cfg = lambda f: list(f) if isinstance(f, (list, tuple)) else f  # noqa: E731
+        return dict(super().get_config(), height_factor=as_cfg(self.height_factor), width_factor=as_cfg(self.width_factor),
+                    fill_mode=self.fill_mode, interpolation=self.interpolation, seed=self.seed, fill_value=self.fill_value)
 
 
 class Rescaling(Layer):
@@ -967,10 +1125,20 @@ class SyncBatchNormalization(BatchNormalization):
         super().__init__(*args, **kw)
 
 
+class _Preprocessing:
+    """``keras.layers.experimental.preprocessing``: where TF 2.3 - 2.5 kept the preprocessing layers."""
+
+    RandomFlip = RandomFlip
+    RandomCrop = RandomCrop
+    RandomTranslation = RandomTranslation
+    Rescaling = Rescaling
+
+
 class _Experimental:
     """``keras.layers.experimental``"""
 
     SyncBatchNormalization = SyncBatchNormalization
+    preprocessing = _Preprocessing()
 
 
 experimental = _Experimental()
@@ -1090,7 +1258,8 @@ def multiply(inputs, **kw):
 
 LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
-    Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, Rescaling, ZeroPadding2D, BatchNormalization,
+    Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
+    ZeroPadding2D, BatchNormalization,
     SyncBatchNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)

@@ -981,18 +981,19 @@ class Sequential(Model):
 
 
 def _copy_rng_streams(src, dst):
-    """A replica clone's Dropout layers draw from their originals' streams (the replicas then differ by
-    the replica id in the key alone), not from the creation indices the clone's own layers took."""
-    from .layers import Dropout
+    """A replica clone's seeded layers (Dropout, the random image layers) draw from their originals' streams
+    (the replicas then differ by the replica id in the key alone), not from the creation indices the clone's
+    own layers took."""
+    from .layers import _CallCounterRNG
 
     def walk(m):
         for l in getattr(m, "layers", []):
             yield l
             yield from walk(l)
 
-    a = [l for l in walk(src) if isinstance(l, Dropout)]
-    b = [l for l in walk(dst) if isinstance(l, Dropout)]
-    assert len(a) == len(b), "a model clone has other Dropout layers than its original"
+    a = [l for l in walk(src) if isinstance(l, _CallCounterRNG)]
+    b = [l for l in walk(dst) if isinstance(l, _CallCounterRNG)]
+    assert len(a) == len(b), "a model clone has other seeded layers than its original"
     for la, lb in zip(a, b):
         lb._rng_stream = la._rng_stream
 
