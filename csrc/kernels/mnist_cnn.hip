@@ -1388,26 +1388,30 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   // itself from the other quarters' tagged partials; otherwise the last to arrive runs it
   const bool tagged = a.head == 1 && a.dp2_fwd;
   float* sown = red + 16 * 128 + 4;   // [128] this quarter's own partial
-  if (tid < 32) {
-    f4 hsum = zero4();
+  // the row-group sum ((r0 + r1) + r2) + ... + r15 of each of the 128 outputs, by wave 0 alone while
+  // everybody waits for it
+  if (tagged) {
+    // all 64 lanes, two outputs each (8-B LDS reads, packed adds, two tagged stores): on 32 lanes
+    // with four outputs each this section took 0.40 us, now 0.14 (profiles/mnist_handoff_chain.txt)
+    if (tid < 64) {
+      typedef float f2 __attribute__((ext_vector_type(2)));
+      f2 hsum = {0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < 16; ++k) hsum += ld4(red + k * 128 + 4 * tid);
-    if (!tagged) {
-      // 16-B sc1 store: the image's head may run on another XCD (hand-off below)
-      st4_sc1(buf_rsrc(a.part3 + ((size_t)cq * a.b + bi) * 128, 512), tid * 16, hsum);
-    } else {
-      st4(sown + 4 * tid, hsum);
+      for (int k = 0; k < 16; ++k) hsum += *reinterpret_cast<const f2*>(red + k * 128 + 2 * tid);
+      *reinterpret_cast<f2*>(sown + 2 * tid) = hsum;
       // (value, tag) words, 8-B write-through stores, polled by the other three quarters
-      unsigned long long* p = a.part3t + ((size_t)cq * a.b + bi) * 128 + 4 * tid;
+      unsigned long long* p = a.part3t + ((size_t)cq * a.b + bi) * 128 + 2 * tid;
       const unsigned long long tg = (unsigned long long)tag << 32;
       __hip_atomic_store(p, (unsigned long long)__float_as_uint(hsum.x) | tg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(p + 1, (unsigned long long)__float_as_uint(hsum.y) | tg, __ATOMIC_RELAXED,
                          __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(p + 2, (unsigned long long)__float_as_uint(hsum.z) | tg, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(p + 3, (unsigned long long)__float_as_uint(hsum.w) | tg, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
     }
+  } else if (tid < 32) {
+    f4 hsum = zero4();
+#pragma unroll
+    for (int k = 0; k < 16; ++k) hsum += ld4(red + k * 128 + 4 * tid);
+    // 16-B sc1 store: the image's head may run on another XCD (hand-off below)
+    st4_sc1(buf_rsrc(a.part3 + ((size_t)cq * a.b + bi) * 128, 512), tid * 16, hsum);
   }
   stamp(a.stamps, 6);
   if (a.head == 0) {
@@ -1421,9 +1425,13 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   const int uwave = __builtin_amdgcn_readfirstlane(wave);
   if (uwave == 0) hw = lds_head_weights(hws, lane);
   // the fused backward's conv2-dgrad operands, from LDS, while the hand-off is in flight (waves 1-7
-  // wait for wave 0's head; wave 0's head waits for its polls: the LDS reads are off both paths)
+  // wait for wave 0's head; wave 0's head waits for its polls: the LDS reads are off both paths).
+  // Wave 0 reads them here, behind its partial's stores; waves 1-7 behind the barrier below: in front
+  // of it their 63 ds_read_b128 (63 KB) filled the LDS pipe just when wave 0 reads the 16 row-group
+  // partials that every workgroup of the image waits for (profiles/mnist_handoff_chain.txt)
   f4 bwd[9];
-  if (a.head == 1 && a.dp2_fwd && a.fused_bwd) lds_dgrad_w2(w2d, bwd);
+  const bool dgrad_w2 = a.head == 1 && a.dp2_fwd && a.fused_bwd;
+  if (dgrad_w2 && uwave == 0) lds_dgrad_w2(w2d, bwd);
 
   // ---- hand-off to the image's last quarter workgroup (MI355X_MICROARCH.md, inter-workgroup
   // visibility, first table row): the storing wave drains its sc1 stores, a workgroup barrier,
@@ -1441,6 +1449,7 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
     }
   }
   lds_barrier();  // (tagged: this quarter's own partial in LDS)
+  if (dgrad_w2 && uwave != 0) lds_dgrad_w2(w2d, bwd);
   const bool last = tagged || s_last[0] != 0;  // (tagged: every quarter runs the head)
   float* sdh = red;  // [128] dH of this image (the dense1 row-group scratch is free now)
   if (last && uwave == 0) {
