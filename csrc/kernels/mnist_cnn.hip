@@ -1189,8 +1189,14 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   // compile-time strides of 64 rows (a feature split by row group, 25 consecutive features per
   // thread, cost ~8 VALU of 64-bit address arithmetic per load: 200 per wave).  The 25 16-B loads
   // per thread (205 KB per workgroup, ~1.3 us of the CU's texture-address rate) are spread over the
-  // conv phases in small groups: issued back to back they fill the CU's vector-memory queue and
-  // every wave stalls behind them (measured: conv1 3.4-4.4 us instead of ~1 us).
+  // conv phases: issued back to back they fill the CU's vector-memory queue and every wave stalls
+  // behind them (conv1 done at 3.4-4.4 us).  What the spread stream still costs was measured with two
+  // diagnostic builds (profiles/mnist_w3_stream.txt): without the loads the dense1 partial is
+  // 0.64 us earlier (conv1 done 3.44 -> 3.16 -- conv1 is NOT ~1 us without them --, conv2's last
+  // waves 0.26 earlier); with 25 loads of one hot address 0.24: 0.40 us of the 0.64 is the ISSUE of
+  // the 200 wave loads, not their data.  So each load sits where its wave waits anyway: in conv1 one
+  // behind every pair of MFMAs (the pipe is busy 64 clk with them), in conv2 between a tap's LDS
+  // operand reads and its MFMAs (under the LDS latency).
   const int n4 = (tid & 31) * 4, rg = tid >> 5;
   f4 w3v[25];
   // one buffer resource over this quarter's W3 rows; the per-load stride rides in the SGPR offset
@@ -1198,6 +1204,12 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   const auto w3r = buf_rsrc(a.W + a.ow3 + (size_t)16 * cq * 128, (unsigned)((1600 - 16 * cq) * 128 * 4));
   const int w3vo = (rg * 128 + n4) * 4;
   auto ldw3 = [&](int j) { w3v[j] = ld4_buf(w3r, w3vo, j * 64 * 128 * 4); };
+  // one load (scheduled where it stands): j = 0 .. 5 here, 6 .. 15 in conv1, 16 .. 24 in conv2
+  auto ldw3_here = [&](int j) {
+    __builtin_amdgcn_sched_barrier(0);
+    ldw3(j);
+    __builtin_amdgcn_sched_barrier(0);
+  };
 #pragma unroll
   for (int j = 0; j < 6; ++j) ldw3(j);
   // ---- conv1 on MFMA (K = 9 taps padded to 12): rows = the conv1 positions in pool-window-major
@@ -1266,18 +1278,17 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
       for (int s3 = 0; s3 < 3; ++s3)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-          if (!live(it, u)) continue;
+          if (live(it, u)) {
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt) acc[u][nt] = mfma16x16x4(xa[it & 1][u][s3], bw[nt][s3], acc[u][nt]);
+            for (int nt = 0; nt < 2; ++nt) acc[u][nt] = mfma16x16x4(xa[it & 1][u][s3], bw[nt][s3], acc[u][nt]);
+          }
+          // one W3 load behind each of the first five MFMA pairs of iterations 0 and 1 (a pair that is
+          // not live on waves 4-7 still issues its load: every wave issues all 25 on every path)
+          if (it < 2 && 2 * s3 + u < 5) ldw3_here(6 + 5 * it + 2 * s3 + u);
         }
       __builtin_amdgcn_sched_barrier(0);
       if (it < 2) load_x((it + 1) & 1, it + 1);
       __builtin_amdgcn_sched_barrier(0);
-      if (it < 2) {
-#pragma unroll
-        for (int j = 6 + 5 * it; j < 11 + 5 * it; ++j) ldw3(j);
-        __builtin_amdgcn_sched_barrier(0);
-      }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         if (!live(it, u)) continue;
@@ -1314,7 +1325,10 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   lds_barrier();  // P1 / A1 in LDS; the W3 prefetch loads stay in flight
   stamp(a.stamps, 4);
   // ---- conv2 on MFMA: wave w < 7 takes row tile w (windows 4w .. 4w+3); the last 9 W3 loads
-  // ride along, one per tap ----
+  // ride along, one per tap, each BEHIND the tap's four LDS operand reads and in front of its
+  // MFMAs: the wave waits there for the LDS anyway.  Behind the MFMAs (in front of the next tap's
+  // reads) the load's issue held up those reads: conv2's MFMAs ended 0.2-0.3 us later
+  // (profiles/mnist_w3_stream.txt) ----
   if (wave < 7) {
     const int wi = wave * 4 + (i >> 2), q = i & 3;
     const bool valid = wi < 25;
@@ -1327,18 +1341,20 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
 #pragma unroll
     for (int kk = 0; kk < 9; ++kk) {
       const int kh = kk / 3, kw = kk % 3;
+      f4 av[2], bv[2];
 #pragma unroll
-      for (int cb = 0; cb < 32; cb += 16) {
-        const f4 av = ld4(ab + (kh * 13 + kw) * kP1Stride + cb);
-        const f4 bv = ld4(bb + ((kk * 32 + cb) / 4) * 64);
-        acc0 = mfma16x16x4(av.x, bv.x, acc0);
-        acc1 = mfma16x16x4(av.y, bv.y, acc1);
-        acc0 = mfma16x16x4(av.z, bv.z, acc0);
-        acc1 = mfma16x16x4(av.w, bv.w, acc1);
+      for (int h = 0; h < 2; ++h) {
+        av[h] = ld4(ab + (kh * 13 + kw) * kP1Stride + 16 * h);
+        bv[h] = ld4(bb + ((kk * 32 + 16 * h) / 4) * 64);
       }
-      __builtin_amdgcn_sched_barrier(0);
-      ldw3(16 + kk);
-      __builtin_amdgcn_sched_barrier(0);
+      ldw3_here(16 + kk);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        acc0 = mfma16x16x4(av[h].x, bv[h].x, acc0);
+        acc1 = mfma16x16x4(av[h].y, bv[h].y, acc1);
+        acc0 = mfma16x16x4(av[h].z, bv[h].z, acc0);
+        acc1 = mfma16x16x4(av[h].w, bv[h].w, acc1);
+      }
     }
     const f4 acc = acc0 + acc1;
     stamp(a.stamps, 5);
