@@ -12,6 +12,7 @@
 #include "kernels/dropout.h"
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
+#include "kernels/groupnorm.h"
 #include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
@@ -1463,9 +1464,111 @@ at::Tensor xent_bwd(at::Tensor z, at::Tensor labels, at::Tensor g) {
                         g.data_ptr<float>(), dz.data_ptr<float>(), cur_stream());
   return dz;
 }
+
+// ---- group normalisation (kernels/groupnorm.h) over a channels-last [N, ..., C] tensor
+struct GnShape {
+  int64_t N, P, C;
+  tdl::GnDType dt;
+  tdl::GnPlan plan;
+};
+GnShape gn_check(const at::Tensor& x, int64_t G, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() >= 2, what, ": contiguous [N, ..., C] GPU tensor expected");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, what, ": float32 or bfloat16 expected");
+  TORCH_CHECK(x.numel() > 0, what, ": empty tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, what, ": 16-byte aligned data expected");
+  GnShape sh;
+  sh.N = x.size(0);
+  sh.C = x.size(-1);
+  sh.P = x.numel() / (sh.N * sh.C);
+  TORCH_CHECK(G >= 1 && sh.C % G == 0, what, ": groups must divide the channel count");
+  TORCH_CHECK(sh.C <= 16384 && sh.N * sh.C <= (int64_t(1) << 24), what, ": C <= 16384 and N * C <= 2^24 expected");
+  sh.dt = x.scalar_type() == at::kFloat ? tdl::GnDType::kF32 : tdl::GnDType::kBF16;
+  sh.plan = tdl::gn_plan(sh.P, (int)sh.C, sh.dt);
+  // 256 threads each: a grid of 2^32 threads and more does not launch
+  TORCH_CHECK(sh.N * sh.plan.colblocks * sh.plan.chunks < (int64_t(1) << 24), what, ": 2^24 workgroups or more");
+  return sh;
+}
+const float* gn_param(const c10::optional<at::Tensor>& t, int64_t C, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == C, what,
+              ": f32 [C] GPU parameters expected");
+  return t->data_ptr<float>();
+}
+at::Tensor gn_ws(const c10::optional<std::vector<at::Tensor>>& ws, size_t i, at::IntArrayRef shape,
+                 const at::TensorOptions& o) {
+  if (!ws.has_value()) return fresh(shape, o);
+  TORCH_CHECK(i < ws->size(), "group_norm: workspace list too short");
+  const at::Tensor& t = (*ws)[i];
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == o.dtype().toScalarType() &&
+                  t.numel() == c10::multiply_integers(shape),
+              "group_norm: workspace tensor ", i, " has the wrong dtype or size");
+  return t;
+}
+
+// (y, stats f64 [N][G][2] = mean, 1/sqrt(var + eps), part, coef).  phases / ws: run a subset of the three
+// launches on the buffers (y, stats, part, coef) of an earlier call (timing each launch alone)
+std::vector<at::Tensor> gn_forward(at::Tensor x, int64_t G, c10::optional<at::Tensor> gamma,
+                                   c10::optional<at::Tensor> beta, double eps, int64_t phases,
+                                   c10::optional<std::vector<at::Tensor>> ws) {
+  const GnShape sh = gn_check(x, G, "group_norm");
+  auto d = x.options().dtype(at::kDouble);
+  auto y = gn_ws(ws, 0, x.sizes(), x.options());
+  auto stats = gn_ws(ws, 1, {sh.N, G, 2}, d);
+  auto part = gn_ws(ws, 2, {sh.N, sh.plan.chunks, 2, sh.C}, d);
+  auto coef = gn_ws(ws, 3, {2, sh.N, sh.C}, x.options().dtype(at::kFloat));
+  tdl::gn_forward(x.data_ptr(), y.data_ptr(), sh.dt, sh.N, sh.P, (int)sh.C, (int)G, gn_param(gamma, sh.C, "group_norm"),
+                  gn_param(beta, sh.C, "group_norm"), eps, part.data_ptr<double>(), stats.data_ptr<double>(),
+                  coef.data_ptr<float>(), cur_stream(), (int)phases);
+  return {y, stats, part, coef};
+}
+
+// (dx, dgamma, dbeta, part, coef).  dgamma_out / dbeta_out: f32 [C] tensors the parameter gradients are
+// ADDED into (a trainer's slab views); the returned dgamma / dbeta are then those tensors
+std::vector<at::Tensor> gn_backward(at::Tensor dy, at::Tensor x, int64_t G, c10::optional<at::Tensor> gamma,
+                                    at::Tensor stats, c10::optional<at::Tensor> dgamma_out,
+                                    c10::optional<at::Tensor> dbeta_out, int64_t phases,
+                                    c10::optional<std::vector<at::Tensor>> ws) {
+  const GnShape sh = gn_check(x, G, "group_norm backward");
+  gn_check(dy, G, "group_norm backward");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.sizes() == x.sizes(), "group_norm backward: dy/x mismatch");
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() && stats.scalar_type() == at::kDouble &&
+                  stats.numel() == sh.N * G * 2,
+              "group_norm backward: stats must be f64 [N][G][2]");
+  auto f = x.options().dtype(at::kFloat);
+  auto dx = gn_ws(ws, 0, x.sizes(), x.options());
+  auto part = gn_ws(ws, 1, {sh.N, sh.plan.chunks, 2, sh.C}, x.options().dtype(at::kDouble));
+  auto coef = gn_ws(ws, 2, {3, sh.N, sh.C}, f);
+  auto check_out = [&](const c10::optional<at::Tensor>& t) {
+    if (!t.has_value() || !t->defined()) return (float*)nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->numel() == sh.C,
+                "group_norm backward: gradient outputs must be contiguous f32 [C]");
+    return t->data_ptr<float>();
+  };
+  float* pg = check_out(dgamma_out);
+  float* pb = check_out(dbeta_out);
+  auto out = fresh({2, sh.C}, f);
+  float* o = out.data_ptr<float>();
+  const int acc = (pg ? 1 : 0) | (pb ? 2 : 0);
+  tdl::gn_backward(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), sh.dt, sh.N, sh.P, (int)sh.C, (int)G,
+                   gn_param(gamma, sh.C, "group_norm backward"), stats.data_ptr<double>(), part.data_ptr<double>(),
+                   coef.data_ptr<float>(), pg ? pg : o, pb ? pb : o + sh.C, acc, cur_stream(), (int)phases);
+  return {dx, pg ? *dgamma_out : out[0], pb ? *dbeta_out : out[1], part, coef};
+}
 }  // namespace
 
 void register_ops(pybind11::module& m) {
+  m.def("gn_forward", &gn_forward, "channels-last group normalisation forward: (y, stats, part, coef)",
+        pybind11::arg("x"), pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
+        pybind11::arg("eps"), pybind11::arg("phases") = 7, pybind11::arg("ws") = pybind11::none());
+  m.def("gn_backward", &gn_backward, "channels-last group normalisation backward: (dx, dgamma, dbeta, part, coef)",
+        pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("groups"), pybind11::arg("gamma"),
+        pybind11::arg("stats"), pybind11::arg("dgamma_out") = pybind11::none(),
+        pybind11::arg("dbeta_out") = pybind11::none(), pybind11::arg("phases") = 7,
+        pybind11::arg("ws") = pybind11::none());
+  m.def("gn_plan", [](int64_t P, int64_t C, bool bf16) {
+    const tdl::GnPlan p = tdl::gn_plan(P, (int)C, bf16 ? tdl::GnDType::kBF16 : tdl::GnDType::kF32);
+    return std::vector<int64_t>{p.vec, p.cols, p.tc, p.rl, p.colblocks, p.rows_wg, p.chunks};
+  }, "group normalisation plan for (P, C, dtype): vec, cols, tc, rl, colblocks, rows_wg, chunks");
   m.def("xent_fwd", &xent_fwd, "sparse softmax cross-entropy forward: (loss, logsumexp)");
   m.def("xent_bwd", &xent_bwd, "sparse softmax cross-entropy backward: (softmax - onehot) * g");
   m.def("xent_head", &xent_head, "fused loss head: mean-reduced sparse softmax cross-entropy, its dlogits and "

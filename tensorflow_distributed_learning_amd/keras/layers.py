@@ -1144,6 +1144,100 @@ class _Experimental:
 experimental = _Experimental()
 
 
+class GroupNormalization(Layer):
+    """tf.keras.layers.GroupNormalization (Wu & He): each sample is normalised over ``groups`` groups of
+    consecutive channels and all its other non-batch dimensions.  The statistics belong to one sample:
+    training and inference are the same computation, there are no moving statistics, and the result
+    does not depend on the per-replica batch or on the number of replicas.  ``groups=-1``: one group per
+    channel (instance normalisation).  On the GPU the hand-written channels-last kernels run it
+    (ops/groupnorm.py): f32 or bf16 data (``mixed_bfloat16``), gamma / beta in f32."""
+
+    def __init__(self, groups=32, axis=-1, epsilon=1e-3, center=True, scale=True, beta_initializer="zeros",
+                 gamma_initializer="ones", beta_regularizer=None, gamma_regularizer=None, **kw):
+        super().__init__(**kw)
+        if isinstance(groups, bool) or not isinstance(groups, int) or not (groups == -1 or groups >= 1):
+            raise ValueError(f"{type(self).__name__}: groups must be -1 or a positive integer, got {groups!r}")
+        self.groups = groups
+        self.axis = axis
+        self.epsilon = float(epsilon)
+        self.center, self.scale = center, scale
+        self.beta_initializer = _init.get(beta_initializer)
+        self.gamma_initializer = _init.get(gamma_initializer)
+        self.beta_regularizer = self._regularizer(beta_regularizer)
+        self.gamma_regularizer = self._regularizer(gamma_regularizer)
+
+    @staticmethod
+    def _regularizer(r):
+        """A regularizer object, or its ``get_config`` form ``{"class_name": "L1L2", "config": {l1, l2}}``."""
+        if isinstance(r, dict):
+            from . import regularizers as _reg
+
+            if r.get("class_name") != "L1L2":
+                raise ValueError(f"GroupNormalization: unknown regularizer config {r!r}")
+            return _reg.L1L2(**r.get("config", {}))
+        return r
+
+    @staticmethod
+    def _regularizer_config(r):
+        from . import regularizers as _reg
+
+        if type(r) is _reg.L1L2:
+            return {"class_name": "L1L2", "config": {"l1": r.l1, "l2": r.l2}}
+        return r  # (another callable: kept as the object, such a config does not survive JSON)
+
+    def _groups_for(self, c):
+        g = c if self.groups == -1 else self.groups
+        if c % g != 0:
+            raise ValueError(f"{self.name}: groups = {g} does not divide the {c} channels of axis {self.axis}")
+        return g
+
+    def build(self, input_shape):
+        if input_shape[self.axis] is None:
+            raise ValueError(f"{self.name}: axis {self.axis} of the input must have a known size")
+        c = int(input_shape[self.axis])
+        self._groups_for(c)
+        self.gamma = self.add_weight("gamma", (c,), initializer=self.gamma_initializer,
+                                     regularizer=self.gamma_regularizer) if self.scale else None
+        self.beta = self.add_weight("beta", (c,), initializer=self.beta_initializer,
+                                    regularizer=self.beta_regularizer) if self.center else None
+        self.built = True
+
+    def call(self, x, training=None):
+        from ..ops import groupnorm as _gn
+
+        x = _autocast_input(x)
+        axis = self.axis % x.dim()
+        if axis == 0:
+            raise ValueError(f"{self.name}: axis 0 is the batch")
+        h = x if axis == x.dim() - 1 else x.movedim(axis, -1)
+        g = self._groups_for(int(h.shape[-1]))
+        gt = self._grad_targets() if _gn.supported(h, g) and not _gn.use_torch() else None
+        y = _gn.group_norm(h, g, self.gamma.value if self.gamma is not None else None,
+                           self.beta.value if self.beta is not None else None, self.epsilon, grad_out=gt)
+        return y if axis == x.dim() - 1 else y.movedim(-1, axis)
+
+    def _grad_targets(self):
+        """(gamma, beta) slab views the backward kernel adds into directly, or None."""
+        if not self.trainable:
+            return None
+        t = tuple(v.grad_target() if v is not None else None for v in (self.gamma, self.beta))
+        if any(tt is None and v is not None for tt, v in zip(t, (self.gamma, self.beta))):
+            return None
+        return t
+
+    def compute_output_shape(self, s):
+        return s
+
+    def get_config(self):
+        cfg = dict(super().get_config(), groups=self.groups, axis=self.axis, epsilon=self.epsilon,
+                   center=self.center, scale=self.scale, beta_initializer=_init.serialize(self.beta_initializer),
+                   gamma_initializer=_init.serialize(self.gamma_initializer))
+        for k in ("beta_regularizer", "gamma_regularizer"):  # (only when set, as the other layers' configs)
+            if getattr(self, k) is not None:
+                cfg[k] = self._regularizer_config(getattr(self, k))
+        return cfg
+
+
 class LayerNormalization(Layer):
     def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, **kw):
         super().__init__(**kw)
@@ -1260,7 +1354,7 @@ LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
-    SyncBatchNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
 __all__ = sorted(LAYER_CLASSES) + ["Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]
