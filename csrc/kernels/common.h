@@ -126,4 +126,25 @@ __device__ __forceinline__ void stamp(unsigned long long* buf, int k) {
     buf[((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 8 + k] = __builtin_amdgcn_s_memrealtime();
 }
 
+// The wave-uniform values v... are in SGPRs where this stands (an empty asm statement per value that
+// reads and "writes" it).  At a kernel's entry, on values that come from kernel arguments: every
+// scalar load behind them is issued there, ahead of one wait, and none is sunk into a later branch.
+// (a pointer passes through the asm statement as a GLOBAL one: a generic pointer out of an asm
+// statement would make every access through it a flat_ instruction)
+template <class T>
+__device__ __forceinline__ void pin_sgpr(T& v) {
+  asm volatile("" : "+s"(v));
+}
+template <class T>
+__device__ __forceinline__ void pin_sgpr(T*& v) {
+  auto g = (__attribute__((address_space(1))) T*)v;
+  asm volatile("" : "+s"(g));
+  v = (T*)g;
+}
+template <class T, class... U>
+__device__ __forceinline__ void pin_sgpr(T& v, U&... u) {
+  pin_sgpr(v);
+  pin_sgpr(u...);
+}
+
 }  // namespace tdl

@@ -1120,7 +1120,42 @@ __device__ __forceinline__ void store_saved_fwd(const MnistArgs& a, int bi, int 
   }
 }
 
-__global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
+#ifdef TDL_DIAG_ARGS_STAMP
+// diagnostics build: launch-head stamps per wave, behind every other stamp region (scripts/stamps_mnist.py,
+// stamps_step.py): the fused kernel's [grid][8 waves][2] = entry, arguments landed; then KF-X's
+// [kFxBlocks][8 waves][4] = entry, arguments landed, first operand load about to issue
+__device__ __forceinline__ unsigned long long* args_stamps(unsigned long long* buf, int b, bool fx) {
+  if (buf == nullptr || (threadIdx.x & 63) != 0) return nullptr;
+  unsigned long long* p = buf + (size_t)b * 4 * 104 + kFxBlocks * 16 + (size_t)b * 4 * 8;
+  const size_t w = (size_t)blockIdx.x * 8 + (threadIdx.x >> 6);
+  return fx ? p + (size_t)b * 4 * 16 + w * 4 : p + w * 2;
+}
+#endif
+
+// Launch head: the fields that stand in front of the first vector loads (the block map, the index load
+// and the W1 / W2 / bias / tag staging loads) are LEADING scalar kernel parameters, 14 dwords in one
+// 64-byte line of the kernarg segment.  The file is compiled with kernel-argument preloading
+// (build_native.py: the dispatcher places those 14 dwords in SGPRs before a wave starts; a compiler-made
+// prologue loads them, ahead of ONE wait, where the firmware does not), so the first loads wait for no
+// argument.  Read out of the by-value MnistArgs the same fields came in two dependent scalar round
+// trips to two far lines (variant / b for the block map, then X / idx / W / the offsets), each an L2
+// hit at best: the scalar cache is invalidated at every kernel start.  The copy `a` carries them to the
+// rest of the kernel (the same values as a0's: mnist_fwd_conv fills both from one MnistArgs).  pin_sgpr
+// keeps their fetch in one place, in front of the block map's branch.  The same block without
+// preloading, fetched in one batch, measured 0.4-1 % SLOWER than the parent
+// (profiles/mnist_launch_head.txt).
+__global__ __launch_bounds__(512) void k_fwd_conv(const int* idx, const float* X, float* W, unsigned* ep, int b,
+                                                  int variant, int ow1, int ob1, int ow2, int ob2, MnistArgs a0) {
+#ifdef TDL_DIAG_ARGS_STAMP
+  const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
+#endif
+  MnistArgs a = a0;
+  a.idx = idx, a.X = X, a.W = W, a.ep = ep, a.b = b, a.variant = variant;
+  a.ow1 = ow1, a.ob1 = ob1, a.ow2 = ow2, a.ob2 = ob2;
+  pin_sgpr(a.idx, a.X, a.W, a.ep, a.b, a.variant, a.ow1, a.ob1, a.ow2, a.ob2);
+#ifdef TDL_DIAG_ARGS_STAMP
+  const unsigned long long t_landed = __builtin_amdgcn_s_memrealtime();
+#endif
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* xs = sm;
   float* w1s = xs + 784;
@@ -1136,21 +1171,15 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   float* dCs = hws + kHeadW;               // fused_bwd: the dC2 grid (kDcF x kDcF cells)
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, g = lane >> 4;
-  int bi = blockIdx.x >> 2, cq = blockIdx.x & 3;
-  if ((a.variant & kMnistVariantXcd) && (a.b & 7) == 0) {
-    // block B -> XCD class B % 8, slot B / 8: each class holds b / 8 whole images (4 slots each)
-    const int x = blockIdx.x & 7, sl = blockIdx.x >> 3;
-    bi = x * (a.b >> 3) + (sl >> 2);
-    cq = sl & 3;
-  }
-  // waves w and w + 4 share a SIMD; the younger half (4-7) loses the VALU issue arbitration in every
-  // phase and reaches each barrier last (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if ((a.variant & kMnistVariantPrio) && __builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);
-  stamp(a.stamps, 0);
-  // ---- staging: all global loads first ----
+  // block B -> XCD class B % 8, slot B / 8: each class holds b / 8 whole images (4 slots each); else 4
+  // consecutive blocks per image (behind the argument fetch, which pin_sgpr keeps in one place above it)
+  const bool xcd = (a.variant & kMnistVariantXcd) && (a.b & 7) == 0;
+  const int xsl = blockIdx.x >> 3;
+  const int bi = xcd ? (int)(blockIdx.x & 7) * (a.b >> 3) + (xsl >> 2) : (int)(blockIdx.x >> 2);
+  const int cq = xcd ? xsl & 3 : (int)(blockIdx.x & 3);
+  // ---- staging: all global loads first; the index and the weights (preloaded arguments only) in front
+  // of the first use of an argument that is fetched (stamps, Y), the sample's loads behind it ----
   const int sample = a.idx[bi];
-  const f4 vx = ld4(a.X + (size_t)sample * 784 + min(tid, 195) * 4);
-  const int label = a.Y[sample];  // for the head (this image's last quarter workgroup)
   const float vw1 = tid < 288 ? a.W[a.ow1 + tid] : a.W[a.ob1 + min(tid - 288, 31)];
   f4 vw2[3];
 #pragma unroll
@@ -1164,7 +1193,16 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
   const float b2v = a.W[a.ob2 + 16 * cq + (lane & 15)];
   // (a VGPR: a readfirstlane here would wait for the whole staging round trip before the LDS stores)
   const uint32_t tag = a.ep[0] + 1u;  // (advanced by KC / KF)
+  // (phase stamp 0, "start": behind the first loads' issue, where the fetched `stamps` is waited for anyway.
+  // A time taken at the entry and stored here cost every wave an s_memrealtime: 0.1-0.2 us per step)
+  stamp(a.stamps, 0);
+  const f4 vx = ld4(a.X + (size_t)sample * 784 + min(tid, 195) * 4);
+  const int label = a.Y[sample];  // for the head (this image's last quarter workgroup)
   __builtin_amdgcn_sched_barrier(0);
+  // waves w and w + 4 share a SIMD; the younger half (4-7) loses the VALU issue arbitration in every
+  // phase and reaches each barrier last (MI355X_MICROARCH.md, two waves per SIMD, item 4)
+  // (behind the staging loads' issue: a branch in front of them splits the argument fetch)
+  if ((a.variant & kMnistVariantPrio) && __builtin_amdgcn_readfirstlane(wave) >= 4) __builtin_amdgcn_s_setprio(1);
   if (tid < 196) st4(xs + tid * 4, vx);
   if (tid < 320) w1s[tid] = vw1;
 #pragma unroll
@@ -1181,6 +1219,9 @@ __global__ __launch_bounds__(512) void k_fwd_conv(MnistArgs a) {
     }
   }
   stamp(a.stamps, 1);
+#ifdef TDL_DIAG_ARGS_STAMP
+  if (auto* as = args_stamps(a.stamps, a.b, false)) as[0] = t_entry, as[1] = t_landed;
+#endif
   __syncthreads();
   stamp(a.stamps, 2);
   // ---- dense1 operand prefetch, overlapping the convolutions: thread (row group rg, 4 columns n4)
@@ -1658,11 +1699,30 @@ __device__ __forceinline__ void fx_range(const MnistArgs& a, int j, int& lo, int
 }
 
 template <int R>
-__device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sgd, int j);
+__device__ __forceinline__ void finalize_x_body(const MnistArgs& a, const XgmiArgs& xa, int apply_sgd, int j);
 
 // phase stamps of KF-X (diagnostics), after the fused kernel's grid*104 words: per wave, start and end
 template <int R, bool LOOP>
-__global__ __launch_bounds__(512) void k_finalize_x(MnistArgs a, int apply_sgd) {
+// Launch head, as in k_fwd_conv: the slab, the learning rate, every range kind's operand pointers and the
+// switches are leading scalar parameters (15 dwords, one 64-byte line; the first 14 preloaded), and the
+// far fields that a range kind reads in front of its first operand load (the slab offsets, H / dL, ep,
+// stamps) are fetched in one batch ahead of ONE wait, above the range-kind branch.  Read out of
+// MnistArgs where each was used they came in three dependent scalar round trips (lr / b, the offsets
+// and switches, then part2 inside the conv branch) in a kernel of 2.9 us.  The exchange operands stay
+// in a0 (xa: indexed by rank).
+__global__ __launch_bounds__(512) void k_finalize_x(float* W, const float* lr, float* P2, float* dH, float* part2,
+                                                    float* part1, int b, int variant, int apply_sgd, MnistArgs a0) {
+#ifdef TDL_DIAG_ARGS_STAMP
+  const unsigned long long t_entry = __builtin_amdgcn_s_memrealtime();
+#endif
+  MnistArgs a = a0;
+  a.W = W, a.lr = lr, a.P2 = P2, a.dH = dH, a.part2 = part2, a.part1 = part1, a.b = b, a.variant = variant;
+  pin_sgpr(a.W, a.lr, a.P2, a.dH, a.part2, a.part1, a.b, a.variant, apply_sgd, a.stamps, a.ep, a.G, a.H, a.dL, a.ow1,
+           a.ob1, a.ow2, a.ob2, a.ow3, a.ob3, a.ow4, a.ob4, a.nslab);
+#ifdef TDL_DIAG_ARGS_STAMP
+  const unsigned long long t_landed = __builtin_amdgcn_s_memrealtime();
+  if (auto* as = args_stamps(a.stamps, a.b, true)) as[0] = t_entry, as[1] = t_landed;
+#endif
   unsigned long long* sb = a.stamps == nullptr ? nullptr
       : a.stamps + (size_t)a.b * 4 * 104 + ((size_t)blockIdx.x * 8 + (threadIdx.x >> 6)) * 2;
   if (sb != nullptr && (threadIdx.x & 63) == 0) sb[0] = __builtin_amdgcn_s_memrealtime();
@@ -1676,17 +1736,17 @@ __global__ __launch_bounds__(512) void k_finalize_x(MnistArgs a, int apply_sgd) 
   // i.e. 2 instead of 3 resident workgroups per CU)
   if constexpr (LOOP) {
     for (int j = blockIdx.x; j < kFxBlocks; j += gridDim.x) {
-      finalize_x_body<R>(a, apply_sgd, j);
+      finalize_x_body<R>(a, a0.xa, apply_sgd, j);
       __syncthreads();  // (LDS scratch reused by the next range)
     }
   } else {
-    finalize_x_body<R>(a, apply_sgd, blockIdx.x);
+    finalize_x_body<R>(a, a0.xa, apply_sgd, blockIdx.x);
   }
   if (sb != nullptr && (threadIdx.x & 63) == 0) sb[1] = __builtin_amdgcn_s_memrealtime();
 }
 
 template <int R>
-__device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sgd, int j) {
+__device__ __forceinline__ void finalize_x_body(const MnistArgs& a, const XgmiArgs& xa, int apply_sgd, int j) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const float lr = *a.lr;
   const bool xchg = R > 1 && a.xchg && apply_sgd;
@@ -1698,20 +1758,28 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
   float* xdst = nullptr;
   int64_t half = 0;
   if (xchg) {
-    e = __builtin_amdgcn_readfirstlane(a.xa.epoch[j]) + 1u;
-    if (xgmi_failed(a.xa.err)) {
+    e = __builtin_amdgcn_readfirstlane(xa.epoch[j]) + 1u;
+    if (xgmi_failed(xa.err)) {
       // a peer already failed: no exchange, no update, and G is left as the previous step wrote it.
       // The epoch still advances (as in k_xgmi_oneshot / _twoshot), so that after a reset_error
       // every rank's channel epochs stay in step and no rank reads the other parity half
-      if (tid == 0) a.xa.epoch[j] = e;
+      if (tid == 0) xa.epoch[j] = e;
       return;
     }
-    half = (int64_t)(e & 1u) * 2 * a.xa.cap;
-    xdst = a.xa.p.buf[a.xa.rank] + half;
+    half = (int64_t)(e & 1u) * 2 * xa.cap;
+    xdst = xa.p.buf[xa.rank] + half;
   }
   const bool sgd_local = R == 1 && apply_sgd;  // single replica: SGD fused into the reduction
   // (the exchange path applies SGD from the peers' published ranges: G is not read there either)
   const bool keep_g = !((sgd_local || xchg) && (a.variant & kMnistVariantNoG));
+#ifdef TDL_DIAG_ARGS_STAMP
+  auto operands_next = [&] {
+    if (auto* as = args_stamps(a.stamps, a.b, true)) as[2] = __builtin_amdgcn_s_memrealtime();
+  };
+  if (j < kFxDense) operands_next();  // (a dense task: its operand loads follow its address arithmetic)
+#else
+  auto operands_next = [] {};
+#endif
   // ---- this workgroup's gradient range ----
   if (j < kFxW3) {
     // dW3 rows 16 (j >> 1) .. +15, column tiles 4 (j & 1) .. +3: one task per wave of waves 0-3
@@ -1741,6 +1809,7 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
     // images past b read 0 (resource sized to the b images); image stride in the SGPR offset
     const auto p2r = buf_rsrc(a.part2, (unsigned)(a.b * kP2QuadFloats * 4));
     const int vo2 = (grp * kP2QuadFloats + (qd * 64 + 32 * h + c) * 4) * 4;
+    operands_next();
     for (int base = 0; base < a.b; base += 64) {  // 4 images per thread in flight
       f4 v[4];
 #pragma unroll
@@ -1773,6 +1842,7 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
     // rows past `rows` read 0 (resource sized to them); the row stride rides in the SGPR offset
     const auto p1r = buf_rsrc(a.part1, (unsigned)(rows * kMnistPart1Cols * 4));
     const int vo1 = ((4 * wave + rg) * kMnistPart1Cols + o) * 4;
+    operands_next();
     for (int b0 = 0; b0 < rows; b0 += 256) {
       float v[8];
 #pragma unroll
@@ -1795,8 +1865,8 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
   if constexpr (R > 1) {
     if (!xchg) return;
     // ---- exchange with workgroup j of every peer, rank-order sum, SGD of the range ----
-    if (!xgmi_exchange<R>(a.xa.p, a.xa.rank, a.xa.sig_blocks, a.xa.timeout, a.xa.err, 0, j, e)) {
-      if (tid == 0) a.xa.epoch[j] = e;
+    if (!xgmi_exchange<R>(xa.p, xa.rank, xa.sig_blocks, xa.timeout, xa.err, 0, j, e)) {
+      if (tid == 0) xa.epoch[j] = e;
       return;
     }
     int lo, cnt, nseg, stride;
@@ -1813,33 +1883,33 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
       // round every rank copies each share from its owner (bit-identical by construction, and W is
       // written only after both rounds: a timeout leaves it untouched).  2 (R-1)/R of the range
       // crosses the fabric per rank instead of (R-1) x the range.
-      const int64_t res = half + a.xa.cap;
-      float* mine = a.xa.p.buf[a.xa.rank];
+      const int64_t res = half + xa.cap;
+      float* mine = xa.p.buf[xa.rank];
       for (int t = tid; t < tot; t += 512) {
-        if ((t * R) / tot != a.xa.rank) continue;
+        if ((t * R) / tot != xa.rank) continue;
         const int64_t off = off_of(t);
         f4 v[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = ld4(a.xa.p.buf[r] + half + off);
+        for (int r = 0; r < R; ++r) v[r] = ld4(xa.p.buf[r] + half + off);
         f4 acc = v[0];
 #pragma unroll
         for (int r = 1; r < R; ++r) acc += v[r];
         st4(mine + res + off, ld4(a.W + off) - lr * acc);
       }
-      if (!xgmi_exchange<R>(a.xa.p, a.xa.rank, a.xa.sig_blocks, a.xa.timeout, a.xa.err, 1, j, e)) {
-        if (tid == 0) a.xa.epoch[j] = e;
+      if (!xgmi_exchange<R>(xa.p, xa.rank, xa.sig_blocks, xa.timeout, xa.err, 1, j, e)) {
+        if (tid == 0) xa.epoch[j] = e;
         return;
       }
       for (int t = tid; t < tot; t += 512) {
         const int64_t off = off_of(t);
-        st4_sc1(wr, (int)off * 4, ld4(a.xa.p.buf[(t * R) / tot] + res + off));
+        st4_sc1(wr, (int)off * 4, ld4(xa.p.buf[(t * R) / tot] + res + off));
       }
     } else {
       for (int t = tid; t < tot; t += 512) {
         const int64_t off = off_of(t);
         f4 v[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) v[r] = ld4(a.xa.p.buf[r] + half + off);
+        for (int r = 0; r < R; ++r) v[r] = ld4(xa.p.buf[r] + half + off);
         f4 acc = v[0];
 #pragma unroll
         for (int r = 1; r < R; ++r) acc += v[r];
@@ -1849,12 +1919,12 @@ __device__ __forceinline__ void finalize_x_body(const MnistArgs& a, int apply_sg
     // scalar tail of a range (db4: 10 floats), summed by every rank itself in rank order
     for (int t = 4 * n4 + tid; t < cnt; t += 512) {
       const int64_t off = lo + t;
-      float acc = a.xa.p.buf[0][half + off];
+      float acc = xa.p.buf[0][half + off];
 #pragma unroll
-      for (int r = 1; r < R; ++r) acc += a.xa.p.buf[r][half + off];
+      for (int r = 1; r < R; ++r) acc += xa.p.buf[r][half + off];
       a.W[off] -= lr * acc;
     }
-    if (tid == 0) a.xa.epoch[j] = e;
+    if (tid == 0) xa.epoch[j] = e;
   }
 }
 
@@ -1960,7 +2030,8 @@ void mnist_fwd_conv(const MnistArgs& a, hipStream_t s) {
     attr = true;
   }
   const bool fused = a.head == 1 && a.dp2_fwd && a.fused_bwd;
-  hipLaunchKernelGGL(k_fwd_conv, dim3(a.b * 4), dim3(512), (fused ? kLdsFwdFused : kLdsFwd) * sizeof(float), s, a);
+  hipLaunchKernelGGL(k_fwd_conv, dim3(a.b * 4), dim3(512), (fused ? kLdsFwdFused : kLdsFwd) * sizeof(float), s, a.idx,
+                     a.X, a.W, a.ep, a.b, a.variant, a.ow1, a.ob1, a.ow2, a.ob2, a);
 }
 void mnist_finalize(const MnistArgs& a, bool apply_sgd, bool with_dense, hipStream_t s) {
   const int ndb = with_dense ? (kDenseTasks + 3) / 4 : 0;
@@ -1976,7 +2047,8 @@ void mnist_finalize_x(const MnistArgs& a, bool apply_sgd, hipStream_t s) {
   const int kFxBlocks = (a.fx_grid > 0 && a.fx_grid < tdl::kFxBlocks) ? a.fx_grid : tdl::kFxBlocks;
   auto launch = [&](auto rk, auto loop) {
     constexpr int kR = decltype(rk)::value;
-    hipLaunchKernelGGL((k_finalize_x<kR, decltype(loop)::value>), dim3(kFxBlocks), dim3(512), 0, s, a, sgd);
+    hipLaunchKernelGGL((k_finalize_x<kR, decltype(loop)::value>), dim3(kFxBlocks), dim3(512), 0, s, a.W, a.lr, a.P2,
+                       a.dH, a.part2, a.part1, a.b, a.variant, sgd, a);
   };
   auto go = [&](auto rk) {
     if (kFxBlocks < tdl::kFxBlocks) launch(rk, std::true_type{});

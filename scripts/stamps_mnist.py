@@ -40,8 +40,11 @@ def main():
             continue
         # fused kernel: grid * 104 words, then KF-X's (not launched here), then the diagnostics build's
         # "dgrad MFMAs issued" stamp per wave (-DTDL_DIAG_DGRAD_STAMP; zeros in a normal build)
+        # then the launch-head stamps of a -DTDL_DIAG_ARGS_STAMP build: the fused kernel's [grid][8][2] =
+        # entry, arguments landed; KF-X's [FINALIZE_BLOCKS][8][4] (scripts/stamps_step.py prints those)
         diag0 = grid * 104 + M.FINALIZE_BLOCKS * 16
-        buf = torch.zeros(diag0 + grid * 8, dtype=torch.int64, device=dev)
+        args0 = diag0 + grid * 8
+        buf = torch.zeros(args0 + grid * 16 + M.FINALIZE_BLOCKS * 32, dtype=torch.int64, device=dev)
         st.forward_backward(0)
         st.finalize(True)
         st._impl.set_stamps(buf)
@@ -84,7 +87,7 @@ def main():
             for k2, label in enumerate(["bwd dC2 ready", "bwd wgrad done", "bwd dgrad done", "bwd reduced"]):
                 vals = [np.median(relb[:, w, k2]) for w in range(waves)]
                 print(f"  {label:14s}" + " ".join(f"{v:6.2f}" for v in vals))
-            dg = buf[diag0:].view(grid, 8).cpu().numpy().astype(np.int64)
+            dg = buf[diag0:args0].view(grid, 8).cpu().numpy().astype(np.int64)
             if (dg > 0).all():
                 reld = (dg - t0w[:, None]) * 10 / 1000.0
                 print("  bwd dgrad MFMAs" + " ".join(f"{np.median(reld[:, w]):6.2f}" for w in range(waves)))
@@ -93,6 +96,20 @@ def main():
                 tail = np.maximum(relb[:, :4, 2], relb[:, 4:, 2]) - np.maximum(reld[:, :4], reld[:, 4:])
                 print("  exposed dgrad epilogue per SIMD (median / p90 us): " + "  ".join(
                     f"{np.median(tail[:, s]):.2f}/{np.percentile(tail[:, s], 90):.2f}" for s in range(4)))
+        if name == "fwd_conv":
+            ah = buf[args0:args0 + grid * 16].view(grid, 8, 2).cpu().numpy().astype(np.int64)
+            if (ah > 0).all():
+                # launch head, on the same clock as the slots below (0 = the workgroup's first "start" stamp,
+                # which itself waits for the arguments it reads: the entry is earlier)
+                rela = (ah - t0[:, :, None]) * 10 / 1000.0
+                print("  entry         " + " ".join(f"{np.median(rela[:, w, 0]):6.2f}" for w in range(waves)))
+                print("  args landed   " + " ".join(f"{np.median(rela[:, w, 1]):6.2f}" for w in range(waves)))
+                d0 = (ah[:, :, 1] - ah[:, :, 0]) / 100.0
+                d1 = (r[:, :waves, 1] - ah[:, :, 1]) / 100.0
+                print(f"  launch head (all waves, median / p90 us): entry -> args landed {np.median(d0):.2f}/"
+                      f"{np.percentile(d0, 90):.2f}; args landed -> stage-issued {np.median(d1):.2f}/"
+                      f"{np.percentile(d1, 90):.2f}; entry -> stage-issued {np.median(d0 + d1):.2f}/"
+                      f"{np.percentile(d0 + d1, 90):.2f}")
         print("  slot/wave " + " ".join(f"{w:>6d}" for w in range(waves)))
         for s, label in sorted(slots.items(), key=lambda kv: np.median(rel[:, 0, kv[0]])):
             vals = [np.median(rel[:, w, s]) if (r[:, w, s] > 0).all() else float("nan") for w in range(waves)]

@@ -33,10 +33,14 @@ def main():
         st.finalize(True)
     grid, nfx = 4 * b, M.FINALIZE_BLOCKS
     CATS = _cats(nfx)
-    rows, cats, lasts = [], [], []
+    rows, cats, lasts, heads, fheads = [], [], [], [], []
     for rep in range(int(os.environ.get("REPS", "20"))):
         # (+ grid * 8 words: a -DTDL_DIAG_DGRAD_STAMP build stamps there, see stamps_mnist.py)
-        buf = torch.zeros(grid * 104 + nfx * 16 + grid * 8, dtype=torch.int64, device=dev)
+        # (+ grid * 16 + nfx * 32 words: the launch-head stamps of a -DTDL_DIAG_ARGS_STAMP build -- the fused
+        # kernel's [grid][8][2] = entry, arguments landed; KF-X's [nfx][8][4] = entry, arguments landed, first
+        # operand load about to issue)
+        args0 = grid * 104 + nfx * 16 + grid * 8
+        buf = torch.zeros(args0 + grid * 16 + nfx * 32, dtype=torch.int64, device=dev)
         st._impl.set_stamps(buf)
         st.forward_backward(0)
         st.finalize(True)
@@ -46,6 +50,20 @@ def main():
         f = f[f > (1 << 32)]  # (time stamps only: the head's slot 4 holds a poll count)
         x = buf[grid * 104:grid * 104 + nfx * 16].view(nfx, 8, 2).cpu().numpy().astype(np.int64)
         t0 = f.min()
+        fa = buf[args0:args0 + grid * 16].view(grid, 8, 2).cpu().numpy().astype(np.int64)
+        xa = buf[args0 + grid * 16:].view(nfx, 8, 4).cpu().numpy().astype(np.int64)
+        if (fa[:, :, 0] > 0).all():
+            st1 = buf[:grid * 64].view(grid, 8, 8)[:, :, 1].cpu().numpy().astype(np.int64)  # stage-issued
+            fheads.append([np.median(fa[:, :, 1] - fa[:, :, 0]) / 100 if (fa[:, :, 1] > 0).all() else np.nan,
+                           np.median(st1 - fa[:, :, 0]) / 100])
+            hk = []
+            for nm, (lo, hi) in CATS.items():
+                nw = 4 if nm.startswith("dW3") else 2 if nm.startswith("db3") else 8  # waves with a task
+                e, l, o, end = xa[lo:hi, :nw, 0], xa[lo:hi, :nw, 1], xa[lo:hi, :nw, 2], x[lo:hi, :nw, 1]
+                busy = o > 0
+                hk.append([np.median((l - e)[l > 0]) / 100 if (l > 0).any() else np.nan,
+                           np.median((o - e)[busy]) / 100, np.median((end - e)[busy]) / 100])
+            heads.append(hk)
         xs0 = x[:, :, 0].min()
         cats.append([((x[lo:hi, :, 0].min() - xs0) / 100, (np.median(x[lo:hi, :, 0]) - xs0) / 100,
                       (np.median(x[lo:hi, :, 1]) - xs0) / 100, (x[lo:hi, :, 1].max() - xs0) / 100)
@@ -65,6 +83,14 @@ def main():
     print("KF-X blocks, us since KF-X first wave (median over reps): first start / median start / median end / last end")
     for (nm, _), v in zip(CATS.items(), c):
         print(f"  {nm:22s} " + " ".join(f"{t:6.2f}" for t in v))
+    if fheads:
+        fh = np.median(np.array(fheads), axis=0)
+        print(f"launch head, fused kernel (median over waves and reps, us): entry -> args landed {fh[0]:.2f}; "
+              f"entry -> stage-issued {fh[1]:.2f}")
+        print("launch head, KF-X per range kind (busy waves): entry -> args landed / entry -> first operand load / "
+              "entry -> wave end")
+        for (nm, _), v in zip(CATS.items(), np.median(np.array(heads), axis=0)):
+            print(f"  {nm:22s} " + " ".join(f"{t:6.2f}" for t in v))
     ml = np.median(np.array(lasts), axis=0)
     late = np.argsort(ml)[::-1][:12]
     print("latest KF-X blocks (median last-wave end, us): " + ", ".join(f"{j}:{ml[j]:.2f}" for j in late))
