@@ -37,6 +37,9 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 # not, so the kernels are correct either way (profiles/mnist_launch_head.txt).
 HIP_FILE_FLAGS = {
     "mnist_cnn.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=14"],
+    # depthwise.hip: its results are fixed fmaf / add sequences per element; keep them on the scalar f32 VALU
+    # forms (no packed-f32 pairing of two elements' operations)
+    "depthwise.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -13,6 +13,7 @@
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/groupnorm.h"
+#include "kernels/depthwise.h"
 #include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
@@ -1554,6 +1555,138 @@ std::vector<at::Tensor> gn_backward(at::Tensor dy, at::Tensor x, int64_t G, c10:
                    coef.data_ptr<float>(), pg ? pg : o, pb ? pb : o + sh.C, acc, cur_stream(), (int)phases);
   return {dx, pg ? *dgamma_out : out[0], pb ? *dbeta_out : out[1], part, coef};
 }
+
+// ---- depthwise convolution (kernels/depthwise.h): x [N,H,W,C], w f32 [kh,kw,C,dm], y [N,OH,OW,C*dm]
+// geo = (sh, sw, dh, dw, pt, pl)
+struct DwShape {
+  tdl::DwGeom g;
+  tdl::DwDType dt;
+  tdl::DwPlan plan;
+};
+void dw_data(const at::Tensor& t, const char* what, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.dim() == 4 && t.numel() > 0, what, ": ", name,
+              " must be a non-empty contiguous NHWC GPU tensor");
+  TORCH_CHECK(t.scalar_type() == at::kFloat || t.scalar_type() == at::kBFloat16, what, ": ", name,
+              " must be float32 or bfloat16");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, what, ": ", name, " must be 16-byte aligned");
+}
+const float* dw_f32(const c10::optional<at::Tensor>& t, int64_t n, const char* what, const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->numel() == n, what, ": ", name,
+              " must be a contiguous f32 GPU tensor of ", n, " elements");
+  return t->data_ptr<float>();
+}
+// the limits ops/depthwise.py's supported() mirrors
+DwShape dw_check(at::IntArrayRef xs, int64_t kh, int64_t kw, int64_t dm, int64_t OH, int64_t OW,
+                 const std::vector<int64_t>& geo, bool bf16, const char* what) {
+  TORCH_CHECK(xs.size() == 4 && geo.size() == 6, what, ": a [N,H,W,C] shape and (sh, sw, dh, dw, pt, pl) expected");
+  for (int64_t v : xs) TORCH_CHECK(v >= 1 && v < (int64_t(1) << 31), what, ": bad input shape");
+  TORCH_CHECK(kh >= 1 && kw >= 1 && kh * kw <= tdl::kDwMaxTaps, what, ": kh * kw <= 49 expected");
+  TORCH_CHECK(dm >= 1 && dm <= tdl::kDwMaxDm, what, ": depth multiplier 1..8 expected");
+  TORCH_CHECK(xs[3] * dm <= tdl::kDwMaxCout, what, ": C * dm <= 16384 expected");
+  TORCH_CHECK(geo[0] >= 1 && geo[1] >= 1 && geo[2] >= 1 && geo[3] >= 1, what, ": strides and dilations >= 1 expected");
+  TORCH_CHECK(geo[0] < 65536 && geo[1] < 65536 && geo[2] < 65536 && geo[3] < 65536 && geo[4] >= 0 && geo[4] < 65536 &&
+                  geo[5] >= 0 && geo[5] < 65536, what, ": strides, dilations and pads below 65536 expected");
+  TORCH_CHECK(OH >= 1 && OW >= 1 && OH < (int64_t(1) << 31) && OW < (int64_t(1) << 31), what, ": bad output size");
+  DwShape sh;
+  sh.g = tdl::DwGeom{(int)xs[0], (int)xs[1], (int)xs[2], (int)xs[3], (int)OH, (int)OW, (int)kh, (int)kw,
+                     (int)geo[0], (int)geo[1], (int)geo[2], (int)geo[3], (int)geo[4], (int)geo[5], (int)dm};
+  sh.dt = bf16 ? tdl::DwDType::kBF16 : tdl::DwDType::kF32;
+  sh.plan = tdl::dw_plan(sh.g, sh.dt);
+  TORCH_CHECK(sh.plan.fit, what, ": the halo tile of this kernel / stride / dilation does not fit the LDS budget");
+  auto tiles = [&](int64_t h, int64_t w) {
+    return xs[0] * sh.plan.colblocks * ((h + sh.plan.toh - 1) / sh.plan.toh) * ((w + sh.plan.tow - 1) / sh.plan.tow);
+  };
+  TORCH_CHECK(tiles(OH, OW) < (int64_t(1) << 24) && tiles(xs[1], xs[2]) < (int64_t(1) << 24), what,
+              ": 2^24 workgroups or more");
+  return sh;
+}
+
+at::Tensor dw_forward(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, std::vector<int64_t> geo, int64_t OH,
+                      int64_t OW, int64_t act, c10::optional<at::Tensor> out) {
+  const char* what = "depthwise_conv2d";
+  dw_data(x, what, "x");
+  TORCH_CHECK(w.dim() == 4 && w.size(2) == x.size(3), what, ": w must be [kh,kw,C,dm]");
+  const DwShape sh = dw_check(x.sizes(), w.size(0), w.size(1), w.size(3), OH, OW, geo, x.scalar_type() == at::kBFloat16, what);
+  const int64_t cout = x.size(3) * w.size(3);
+  const float* pw = dw_f32(w, w.numel(), what, "w");
+  const float* pb = dw_f32(bias, cout, what, "bias");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pw) % 16 == 0 && reinterpret_cast<uintptr_t>(pb) % 16 == 0, what,
+              ": w and bias must be 16-byte aligned");
+  TORCH_CHECK(act == 0 || act == 1, what, ": act 0 (none) or 1 (ReLU)");
+  auto y = out.has_value() ? *out : fresh({x.size(0), OH, OW, cout}, x.options());
+  if (out.has_value()) {
+    dw_data(y, what, "out");
+    TORCH_CHECK(y.scalar_type() == x.scalar_type() && y.sizes() == at::IntArrayRef({x.size(0), OH, OW, cout}), what,
+                ": out has the wrong dtype or shape");
+  }
+  tdl::dw_forward(x.data_ptr(), pw, pb, y.data_ptr(), sh.dt, sh.g, (int)act, cur_stream());
+  return y;
+}
+
+at::Tensor dw_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W, std::vector<int64_t> geo,
+                    c10::optional<at::Tensor> dy_mask, c10::optional<at::Tensor> out) {
+  const char* what = "depthwise_conv2d dgrad";
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(w.dim() == 4 && w.size(2) * w.size(3) == dy.size(3), what, ": w must be [kh,kw,C,dm], dy [N,OH,OW,C*dm]");
+  const std::vector<int64_t> xs{dy.size(0), H, W, w.size(2)};
+  const DwShape sh = dw_check(xs, w.size(0), w.size(1), w.size(3), dy.size(1), dy.size(2), geo,
+                              dy.scalar_type() == at::kBFloat16, what);
+  const float* pw = dw_f32(w, w.numel(), what, "w");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(pw) % 16 == 0, what, ": w must be 16-byte aligned");
+  const void* pm = nullptr;
+  if (dy_mask.has_value() && dy_mask->defined()) {
+    dw_data(*dy_mask, what, "dy_mask");
+    TORCH_CHECK(dy_mask->scalar_type() == dy.scalar_type() && dy_mask->sizes() == dy.sizes(), what, ": dy_mask/dy mismatch");
+    pm = dy_mask->data_ptr();
+  }
+  auto dx = out.has_value() ? *out : fresh(xs, dy.options());
+  if (out.has_value()) {
+    dw_data(dx, what, "out");
+    TORCH_CHECK(dx.scalar_type() == dy.scalar_type() && dx.sizes() == at::IntArrayRef(xs), what,
+                ": out has the wrong dtype or shape");
+  }
+  tdl::dw_dgrad(dy.data_ptr(), pm, pw, dx.data_ptr(), sh.dt, sh.g, cur_stream());
+  return dx;
+}
+
+// (dW [kh,kw,C,dm], db [C*dm] or an empty tensor, part).  dw_out / db_out: f32 tensors the gradients are ADDED
+// into (a trainer's slab views); the returned dW / db are then those tensors.  ws: [part] of an earlier call
+std::vector<at::Tensor> dw_wgrad(at::Tensor x, at::Tensor dy, int64_t kh, int64_t kw, std::vector<int64_t> geo,
+                                 c10::optional<at::Tensor> dy_mask, c10::optional<at::Tensor> dw_out,
+                                 c10::optional<at::Tensor> db_out, bool want_db,
+                                 c10::optional<std::vector<at::Tensor>> ws) {
+  const char* what = "depthwise_conv2d wgrad";
+  dw_data(x, what, "x");
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.size(0) == x.size(0) && dy.size(3) % x.size(3) == 0, what,
+              ": x [N,H,W,C] and dy [N,OH,OW,C*dm] of one dtype expected");
+  const int64_t C = x.size(3), dm = dy.size(3) / C, cout = dy.size(3);
+  const DwShape sh = dw_check(x.sizes(), kh, kw, dm, dy.size(1), dy.size(2), geo, x.scalar_type() == at::kBFloat16, what);
+  const void* pm = nullptr;
+  if (dy_mask.has_value() && dy_mask->defined()) {
+    dw_data(*dy_mask, what, "dy_mask");
+    TORCH_CHECK(dy_mask->scalar_type() == dy.scalar_type() && dy_mask->sizes() == dy.sizes(), what, ": dy_mask/dy mismatch");
+    pm = dy_mask->data_ptr();
+  }
+  auto f = x.options().dtype(at::kFloat);
+  const bool aw = dw_out.has_value() && dw_out->defined(), ab = db_out.has_value() && db_out->defined();
+  at::Tensor dW = aw ? *dw_out : fresh({kh, kw, C, dm}, f);
+  at::Tensor db = ab ? *db_out : (want_db ? fresh({cout}, f) : at::empty({0}, f));
+  float* pw = const_cast<float*>(dw_f32(dW, kh * kw * cout, what, "dw_out"));
+  float* pb = (ab || want_db) ? const_cast<float*>(dw_f32(db, cout, what, "db_out")) : nullptr;
+  const int64_t chunks = tdl::dw_wgrad_chunks(sh.g, sh.dt);
+  auto part = gn_ws(ws, 0, {chunks, kh * kw + 1, cout}, x.options().dtype(at::kDouble));
+  tdl::dw_wgrad(x.data_ptr(), dy.data_ptr(), pm, part.data_ptr<double>(), pw, pb, (aw ? 1 : 0) | (ab ? 2 : 0), sh.dt,
+                sh.g, cur_stream());
+  return {dW, db, part};
+}
+
+std::vector<int64_t> dw_plan(std::vector<int64_t> x_shape, int64_t kh, int64_t kw, int64_t dm, int64_t OH, int64_t OW,
+                             std::vector<int64_t> geo, bool bf16) {
+  const tdl::DwPlan p = dw_check(x_shape, kh, kw, dm, OH, OW, geo, bf16, "depthwise_conv2d plan").plan;
+  return {p.vec, p.cols, p.tc, p.colblocks, p.toh, p.tow, p.hh, p.hw, p.ts};
+}
 }  // namespace
 
 void register_ops(pybind11::module& m) {
@@ -1569,6 +1702,20 @@ void register_ops(pybind11::module& m) {
     const tdl::GnPlan p = tdl::gn_plan(P, (int)C, bf16 ? tdl::GnDType::kBF16 : tdl::GnDType::kF32);
     return std::vector<int64_t>{p.vec, p.cols, p.tc, p.rl, p.colblocks, p.rows_wg, p.chunks};
   }, "group normalisation plan for (P, C, dtype): vec, cols, tc, rl, colblocks, rows_wg, chunks");
+  m.def("dw_forward", &dw_forward, "channels-last depthwise convolution forward (+ bias, + ReLU): y",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("geo"), pybind11::arg("out_h"),
+        pybind11::arg("out_w"), pybind11::arg("act") = 0, pybind11::arg("out") = pybind11::none());
+  m.def("dw_dgrad", &dw_dgrad, "channels-last depthwise convolution input gradient: dx",
+        pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("in_h"), pybind11::arg("in_w"), pybind11::arg("geo"),
+        pybind11::arg("dy_mask") = pybind11::none(), pybind11::arg("out") = pybind11::none());
+  m.def("dw_wgrad", &dw_wgrad, "channels-last depthwise convolution weight / bias gradient: (dW, db, part)",
+        pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("kh"), pybind11::arg("kw"), pybind11::arg("geo"),
+        pybind11::arg("dy_mask") = pybind11::none(), pybind11::arg("dw_out") = pybind11::none(),
+        pybind11::arg("db_out") = pybind11::none(), pybind11::arg("want_db") = true,
+        pybind11::arg("ws") = pybind11::none());
+  m.def("dw_plan", &dw_plan, "depthwise convolution plan: vec, cols, tc, colblocks, toh, tow, hh, hw, ts (raises "
+        "for a shape outside the kernels' limits)", pybind11::arg("x_shape"), pybind11::arg("kh"), pybind11::arg("kw"),
+        pybind11::arg("dm"), pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("geo"), pybind11::arg("bf16"));
   m.def("xent_fwd", &xent_fwd, "sparse softmax cross-entropy forward: (loss, logsumexp)");
   m.def("xent_bwd", &xent_bwd, "sparse softmax cross-entropy backward: (softmax - onehot) * g");
   m.def("xent_head", &xent_head, "fused loss head: mean-reduced sparse softmax cross-entropy, its dlogits and "

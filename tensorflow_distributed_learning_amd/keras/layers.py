@@ -22,6 +22,7 @@ from ..parallel.values import Variable, VariableAggregation, VariableSynchroniza
 from ..ops import conv as _conv
 from ..ops import conv_f32 as _conv_f32
 from ..ops import dense as _dense
+from ..ops import depthwise as _dw
 from . import activations as _act
 from . import initializers as _init
 
@@ -493,6 +494,158 @@ class Conv2D(Layer):
                     groups=self.groups, activation=_act.serialize(self.activation), use_bias=self.use_bias,
                     kernel_initializer=_init.serialize(self.kernel_initializer),
                     bias_initializer=_init.serialize(self.bias_initializer))
+
+
+def _regularizer_from(r):
+    return GroupNormalization._regularizer(r)
+
+
+class DepthwiseConv2D(Layer):
+    """tf.keras.layers.DepthwiseConv2D, channels_last: every input channel is convolved with its own
+    ``depth_multiplier`` filters; output channel ``c * depth_multiplier + m`` reads input channel ``c``.  Weights:
+    ``depthwise_kernel [kh, kw, C, dm]`` and ``bias [C * dm]``.  On the GPU it runs on the hand-written stencil
+    kernels (ops/depthwise.py) in f32 or bf16 (``mixed_bfloat16``); the kernel and bias stay f32 there (Keras
+    would round them to bf16).  Not a Conv2D: the Conv2D fusions of keras/fusion.py do not apply to it."""
+
+    def __init__(self, kernel_size, strides=(1, 1), padding="valid", depth_multiplier=1, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, depthwise_initializer="glorot_uniform",
+                 bias_initializer="zeros", depthwise_regularizer=None, bias_regularizer=None,
+                 activity_regularizer=None, depthwise_constraint=None, bias_constraint=None, **kw):
+        super().__init__(**kw)
+        if data_format not in (None, "channels_last"):
+            raise ValueError("only channels_last (NHWC) is supported – the TF default")
+        if depthwise_constraint is not None or bias_constraint is not None:
+            raise ValueError(f"{type(self).__name__}: constraints are not implemented")
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        self.padding = padding.lower()
+        if self.padding not in ("valid", "same"):
+            raise ValueError(f"padding must be 'valid' or 'same', got {padding!r}")
+        self.depth_multiplier = int(depth_multiplier)
+        if self.depth_multiplier < 1:
+            raise ValueError(f"depth_multiplier must be positive, got {depth_multiplier!r}")
+        self.dilation_rate = _pair(dilation_rate)
+        self.activation = _act.get(activation)
+        self.use_bias = use_bias
+        self.depthwise_initializer = _init.get(depthwise_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        self.depthwise_regularizer = _regularizer_from(depthwise_regularizer)
+        self.bias_regularizer = _regularizer_from(bias_regularizer)
+
+    def _build_depthwise(self, cin, bias):
+        kh, kw = self.kernel_size
+        self.depthwise_kernel = self.add_weight("depthwise_kernel", (kh, kw, cin, self.depth_multiplier),
+                                                initializer=self.depthwise_initializer,
+                                                regularizer=self.depthwise_regularizer)
+        self.bias = self.add_weight("bias", (cin * self.depth_multiplier,), initializer=self.bias_initializer,
+                                    regularizer=self.bias_regularizer) if bias else None
+
+    def build(self, input_shape):
+        self._build_depthwise(int(input_shape[-1]), self.use_bias)
+        self.built = True
+
+    def _pads(self, x):
+        if self.padding != "same":
+            return (0, 0, 0, 0)
+        ph = _same_pads(x.shape[1], self.kernel_size[0], self.strides[0], self.dilation_rate[0])
+        pw = _same_pads(x.shape[2], self.kernel_size[1], self.strides[1], self.dilation_rate[1])
+        return (ph[0], ph[1], pw[0], pw[1])
+
+    def _depthwise(self, x, bias, act):
+        """The depthwise step on ``x`` with ``bias`` (a Variable or None) and the fused-activation code ``act``;
+        kernel / bias gradients go straight into the trainer's slab when it is bound."""
+        k, pads = self.depthwise_kernel, self._pads(x)
+        gt = None
+        if self.trainable and not _dw.use_torch() and _dw.supported(x, k.value, self.strides, self.dilation_rate, pads):
+            gt = k.grad_target()
+        gb = bias.grad_target() if (bias is not None and gt is not None) else None
+        if gt is not None and gt.is_contiguous() and (bias is None or gb is not None):
+            return _dw.depthwise_conv2d(x, k.value.detach(), bias.value.detach() if bias is not None else None,
+                                        self.strides, pads, self.dilation_rate, act=act, grad_out=gt, gb_out=gb,
+                                        anchor=k.value)
+        return _dw.depthwise_conv2d(x, k.value, bias.value if bias is not None else None, self.strides, pads,
+                                    self.dilation_rate, act=act)
+
+    def call(self, x, training=None):
+        x = _autocast_input(x)
+        act = _fused_act(self.activation)  # ReLU in the forward epilogue and the backward masks
+        y = self._depthwise(x, self.bias, act)
+        return y if act else self.activation(y)
+
+    def _out_hw(self, s):
+        def o(i, k, st, d):
+            if i is None:
+                return None
+            if self.padding == "same":
+                return -(-i // st)
+            return (i - (k - 1) * d - 1) // st + 1
+
+        return (o(s[1], self.kernel_size[0], self.strides[0], self.dilation_rate[0]),
+                o(s[2], self.kernel_size[1], self.strides[1], self.dilation_rate[1]))
+
+    def compute_output_shape(self, s):
+        return (s[0],) + self._out_hw(s) + (s[3] * self.depth_multiplier if s[3] is not None else None,)
+
+    def get_config(self):
+        cfg = dict(super().get_config(), kernel_size=list(self.kernel_size), strides=list(self.strides),
+                   padding=self.padding, depth_multiplier=self.depth_multiplier,
+                   dilation_rate=list(self.dilation_rate), activation=_act.serialize(self.activation),
+                   use_bias=self.use_bias, depthwise_initializer=_init.serialize(self.depthwise_initializer),
+                   bias_initializer=_init.serialize(self.bias_initializer))
+        for k in ("depthwise_regularizer", "bias_regularizer", "pointwise_regularizer"):  # (only when set)
+            if getattr(self, k, None) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
+
+
+class SeparableConv2D(DepthwiseConv2D):
+    """tf.keras.layers.SeparableConv2D: the depthwise step (no bias, no activation) followed by a 1 x 1 stride-1
+    pointwise convolution with the bias and the activation.  Weights: ``depthwise_kernel``, ``pointwise_kernel
+    [1, 1, C * dm, filters]`` and ``bias [filters]``.  The pointwise step is a private Conv2D over this layer's
+    variables, so it takes exactly Conv2D's dispatch for such a kernel (bf16 MFMA kernels where they apply, the
+    f32-MFMA implicit GEMM otherwise)."""
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", data_format=None, dilation_rate=(1, 1),
+                 depth_multiplier=1, activation=None, use_bias=True, depthwise_initializer="glorot_uniform",
+                 pointwise_initializer="glorot_uniform", bias_initializer="zeros", depthwise_regularizer=None,
+                 pointwise_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 depthwise_constraint=None, pointwise_constraint=None, bias_constraint=None, **kw):
+        super().__init__(kernel_size, strides=strides, padding=padding, depth_multiplier=depth_multiplier,
+                         data_format=data_format, dilation_rate=dilation_rate, activation=activation,
+                         use_bias=use_bias, depthwise_initializer=depthwise_initializer,
+                         bias_initializer=bias_initializer, depthwise_regularizer=depthwise_regularizer,
+                         bias_regularizer=bias_regularizer, depthwise_constraint=depthwise_constraint,
+                         bias_constraint=bias_constraint, **kw)
+        if pointwise_constraint is not None:
+            raise ValueError(f"{type(self).__name__}: constraints are not implemented")
+        self.filters = int(filters)
+        self.pointwise_initializer = _init.get(pointwise_initializer)
+        self.pointwise_regularizer = _regularizer_from(pointwise_regularizer)
+
+    def build(self, input_shape):
+        cin = int(input_shape[-1])
+        self._build_depthwise(cin, False)
+        self.pointwise_kernel = self.add_weight("pointwise_kernel", (1, 1, cin * self.depth_multiplier, self.filters),
+                                                initializer=self.pointwise_initializer,
+                                                regularizer=self.pointwise_regularizer)
+        self.bias = self.add_weight("bias", (self.filters,), initializer=self.bias_initializer,
+                                    regularizer=self.bias_regularizer) if self.use_bias else None
+        # the pointwise step: a Conv2D that owns no variables of its own and is no layer of the model
+        pw = Conv2D(self.filters, 1, activation=self.activation, use_bias=self.use_bias, name=self.name + "/pointwise")
+        pw.kernel, pw.bias, pw.built = self.pointwise_kernel, self.bias, True
+        self._pointwise = pw
+        self.built = True
+
+    def call(self, x, training=None):
+        x = _autocast_input(x)
+        return self._pointwise._conv_call(self._depthwise(x, None, 0), training=training)
+
+    def compute_output_shape(self, s):
+        return (s[0],) + self._out_hw(s) + (self.filters,)
+
+    def get_config(self):
+        return dict(super().get_config(), filters=self.filters,
+                    pointwise_initializer=_init.serialize(self.pointwise_initializer))
 
 
 class _Pooled:
@@ -1351,7 +1504,7 @@ def multiply(inputs, **kw):
 
 
 LAYER_CLASSES = {c.__name__: c for c in (
-    InputLayer, Dense, Conv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
+    InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
     SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
