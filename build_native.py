@@ -40,6 +40,8 @@ HIP_FILE_FLAGS = {
     # depthwise.hip: its results are fixed fmaf / add sequences per element; keep them on the scalar f32 VALU
     # forms (no packed-f32 pairing of two elements' operations)
     "depthwise.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # grouped_conv.hip: the same for its epilogue and its fixed-order partial-sum adds
+    "grouped_conv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -4,6 +4,8 @@
 #include <cstdlib>
 #include <cstdio>
 #include <limits>
+#include <map>
+#include <string>
 #include <c10/hip/HIPStream.h>
 
 #include "kernels/bn.h"
@@ -14,6 +16,7 @@
 #include "kernels/gemm_f32.h"
 #include "kernels/groupnorm.h"
 #include "kernels/depthwise.h"
+#include "kernels/grouped_conv.h"
 #include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
@@ -1687,6 +1690,119 @@ std::vector<int64_t> dw_plan(std::vector<int64_t> x_shape, int64_t kh, int64_t k
   const tdl::DwPlan p = dw_check(x_shape, kh, kw, dm, OH, OW, geo, bf16, "depthwise_conv2d plan").plan;
   return {p.vec, p.cols, p.tc, p.colblocks, p.toh, p.tow, p.hh, p.hw, p.ts};
 }
+
+// ---- grouped convolution (kernels/grouped_conv.h): x [N,H,W,C], w f32 [kh,kw,C/G,F], y [N,OH,OW,F]
+// geo = (sh, sw, dh, dw, pt, pl)
+struct GcShape {
+  tdl::GcGeom g;
+  tdl::GcPlan plan;
+};
+// the limits ops/grouped_conv.py's supported() mirrors
+GcShape gc_check(at::IntArrayRef xs, int64_t F, int64_t G, int64_t kh, int64_t kw, int64_t OH, int64_t OW,
+                 const std::vector<int64_t>& geo, const char* what) {
+  TORCH_CHECK(xs.size() == 4 && geo.size() == 6, what, ": a [N,H,W,C] shape and (sh, sw, dh, dw, pt, pl) expected");
+  for (int64_t v : xs) TORCH_CHECK(v >= 1 && v < (int64_t(1) << 31), what, ": bad input shape");
+  TORCH_CHECK(G >= 1 && F >= 1 && xs[3] % G == 0 && F % G == 0, what, ": C and F must be multiples of groups");
+  TORCH_CHECK(kh >= 1 && kw >= 1 && kh * kw * std::max(xs[3] / G, F / G) <= tdl::kGcMaxRed, what,
+              ": kh * kw * max(C, F) / groups <= 2^20 expected");
+  for (int i = 0; i < 6; ++i)
+    TORCH_CHECK(geo[i] >= (i < 4 ? 1 : 0) && geo[i] < 65536, what, ": strides, dilations >= 1 and pads >= 0, below 65536");
+  TORCH_CHECK(OH >= 1 && OW >= 1, what, ": bad output size");
+  TORCH_CHECK((OH - 1) * geo[0] + (kh - 1) * geo[2] < (int64_t(1) << 28) &&
+                  (OW - 1) * geo[1] + (kw - 1) * geo[3] < (int64_t(1) << 28), what, ": window extent of 2^28 or more");
+  TORCH_CHECK(xs[0] * xs[1] * xs[2] * xs[3] < (int64_t(1) << 31) && xs[0] * OH * OW * F < (int64_t(1) << 31), what,
+              ": 2^31 elements or more");
+  GcShape sh;
+  sh.g = tdl::GcGeom{(int)xs[0], (int)xs[1], (int)xs[2], (int)xs[3], (int)F, (int)G, (int)OH, (int)OW, (int)kh, (int)kw,
+                     (int)geo[0], (int)geo[1], (int)geo[2], (int)geo[3], (int)geo[4], (int)geo[5]};
+  sh.plan = tdl::gconv_plan(sh.g);
+  TORCH_CHECK(tdl::kGcLdsBytes <= 65536 && tdl::kGcWgradLdsBytes <= 65536, what, ": LDS budget");
+  TORCH_CHECK(sh.plan.fwd.tiles < 65536 && sh.plan.dgrad.colblocks < 65536 && sh.plan.ws_elems < (int64_t(1) << 31),
+              what, ": too many column tiles or too large a weight-gradient workspace");
+  return sh;
+}
+tdl::GcDType gc_dtype(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16 ? tdl::GcDType::kBF16 : tdl::GcDType::kF32; }
+const void* gc_mask(const c10::optional<at::Tensor>& m, const at::Tensor& dy, const char* what) {
+  if (!m.has_value() || !m->defined()) return nullptr;
+  dw_data(*m, what, "dy_mask");
+  TORCH_CHECK(m->scalar_type() == dy.scalar_type() && m->sizes() == dy.sizes(), what, ": dy_mask/dy mismatch");
+  return m->data_ptr();
+}
+
+at::Tensor gconv_forward(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, int64_t groups,
+                         std::vector<int64_t> geo, int64_t OH, int64_t OW, int64_t act) {
+  const char* what = "grouped conv2d";
+  dw_data(x, what, "x");
+  TORCH_CHECK(w.dim() == 4 && groups >= 1 && w.size(2) * groups == x.size(3), what, ": w must be [kh,kw,C/groups,F]");
+  const GcShape sh = gc_check(x.sizes(), w.size(3), groups, w.size(0), w.size(1), OH, OW, geo, what);
+  const float* pw = dw_f32(w, w.numel(), what, "w");
+  const float* pb = dw_f32(bias, w.size(3), what, "bias");
+  TORCH_CHECK(act == 0 || act == 1, what, ": act 0 (none) or 1 (ReLU)");
+  auto y = fresh({x.size(0), OH, OW, w.size(3)}, x.options());
+  tdl::gconv_forward(x.data_ptr(), pw, pb, y.data_ptr(), gc_dtype(x), sh.g, (int)act, cur_stream());
+  return y;
+}
+
+at::Tensor gconv_dgrad(at::Tensor dy, at::Tensor w, int64_t groups, int64_t H, int64_t W, std::vector<int64_t> geo,
+                       c10::optional<at::Tensor> dy_mask) {
+  const char* what = "grouped conv2d dgrad";
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(w.dim() == 4 && w.size(3) == dy.size(3), what, ": w must be [kh,kw,C/groups,F], dy [N,OH,OW,F]");
+  const std::vector<int64_t> xs{dy.size(0), H, W, w.size(2) * groups};
+  const GcShape sh = gc_check(xs, w.size(3), groups, w.size(0), w.size(1), dy.size(1), dy.size(2), geo, what);
+  const float* pw = dw_f32(w, w.numel(), what, "w");
+  const void* pm = gc_mask(dy_mask, dy, what);
+  auto dx = fresh(xs, dy.options());
+  tdl::gconv_dgrad(dy.data_ptr(), pm, pw, dx.data_ptr(), gc_dtype(dy), sh.g, cur_stream());
+  return dx;
+}
+
+// dW f32 [kh,kw,C/groups,F] (out, added into when accumulate); dbias f32 [F]: written, or added into when accumulate
+at::Tensor gconv_wgrad(at::Tensor x, at::Tensor dy, int64_t kh, int64_t kw, int64_t groups, std::vector<int64_t> geo,
+                       c10::optional<at::Tensor> dy_mask, c10::optional<at::Tensor> out, bool accumulate,
+                       c10::optional<at::Tensor> dbias) {
+  const char* what = "grouped conv2d wgrad";
+  dw_data(x, what, "x");
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.size(0) == x.size(0), what, ": x and dy of one dtype and batch");
+  const int64_t F = dy.size(3);
+  const GcShape sh = gc_check(x.sizes(), F, groups, kh, kw, dy.size(1), dy.size(2), geo, what);
+  const void* pm = gc_mask(dy_mask, dy, what);
+  auto f = x.options().dtype(at::kFloat);
+  const bool given = out.has_value() && out->defined();
+  at::Tensor dW = given ? *out : fresh({kh, kw, x.size(3) / groups, F}, f);
+  float* pw = const_cast<float*>(dw_f32(dW, kh * kw * (x.size(3) / groups) * F, what, "out"));
+  float* pb = const_cast<float*>(dw_f32(dbias, F, what, "dbias"));
+  auto ws = fresh({sh.plan.ws_elems}, f);
+  tdl::gconv_wgrad(x.data_ptr(), dy.data_ptr(), pm, ws.data_ptr<float>(), pw, pb, accumulate && given ? 1 : 0,
+                   gc_dtype(x), sh.g, cur_stream());
+  return dW;
+}
+
+std::map<std::string, int64_t> gconv_plan(std::vector<int64_t> x_shape, int64_t F, int64_t groups, int64_t kh, int64_t kw,
+                                          int64_t OH, int64_t OW, std::vector<int64_t> geo) {
+  const tdl::GcPlan p = gc_check(x_shape, F, groups, kh, kw, OH, OW, geo, "grouped conv2d plan").plan;
+  std::map<std::string, int64_t> m;
+  auto pass = [&](const std::string& n, const tdl::GcPass& q) {
+    m[n + "_vec"] = q.vec;
+    m[n + "_tiles"] = q.tiles;
+    m[n + "_groups_per_tile"] = q.gpt;
+    m[n + "_tiles_per_group"] = q.tpg;
+    m[n + "_colblocks"] = q.colblocks;
+    m[n + "_pixels_per_tile"] = q.ptile;
+    m[n + "_pixel_tiles"] = q.ptiles;
+    m[n + "_kchunks"] = q.kchunks;
+    m[n + "_mfma"] = q.mfma;
+  };
+  pass("fwd", p.fwd);
+  pass("dgrad", p.dgrad);
+  m["wgrad_rowtiles"] = p.wrowtiles;
+  m["wgrad_itemblocks"] = p.witemblocks;
+  m["wgrad_chunk"] = p.wchunk;
+  m["wgrad_splits"] = p.wsplits;
+  m["wgrad_mfma"] = p.wmfma;
+  return m;
+}
 }  // namespace
 
 void register_ops(pybind11::module& m) {
@@ -1716,6 +1832,20 @@ void register_ops(pybind11::module& m) {
   m.def("dw_plan", &dw_plan, "depthwise convolution plan: vec, cols, tc, colblocks, toh, tow, hh, hw, ts (raises "
         "for a shape outside the kernels' limits)", pybind11::arg("x_shape"), pybind11::arg("kh"), pybind11::arg("kw"),
         pybind11::arg("dm"), pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("geo"), pybind11::arg("bf16"));
+  m.def("gconv_forward", &gconv_forward, "channels-last grouped convolution forward (+ bias, + ReLU): y",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("groups"), pybind11::arg("geo"),
+        pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("act") = 0);
+  m.def("gconv_dgrad", &gconv_dgrad, "channels-last grouped convolution input gradient: dx; dy_mask: dy where mask > 0",
+        pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("groups"), pybind11::arg("in_h"), pybind11::arg("in_w"),
+        pybind11::arg("geo"), pybind11::arg("dy_mask") = pybind11::none());
+  m.def("gconv_wgrad", &gconv_wgrad, "channels-last grouped convolution weight (+ bias) gradient, deterministic "
+        "split reduction: dW [kh,kw,C/groups,F]", pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("kh"),
+        pybind11::arg("kw"), pybind11::arg("groups"), pybind11::arg("geo"), pybind11::arg("dy_mask") = pybind11::none(),
+        pybind11::arg("out") = pybind11::none(), pybind11::arg("accumulate") = false,
+        pybind11::arg("dbias") = pybind11::none());
+  m.def("gconv_plan", &gconv_plan, "grouped convolution plan as a dict (raises for a shape outside the kernels' "
+        "limits); no GPU needed", pybind11::arg("x_shape"), pybind11::arg("filters"), pybind11::arg("groups"),
+        pybind11::arg("kh"), pybind11::arg("kw"), pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("geo"));
   m.def("xent_fwd", &xent_fwd, "sparse softmax cross-entropy forward: (loss, logsumexp)");
   m.def("xent_bwd", &xent_bwd, "sparse softmax cross-entropy backward: (softmax - onehot) * g");
   m.def("xent_head", &xent_head, "fused loss head: mean-reduced sparse softmax cross-entropy, its dlogits and "

@@ -21,6 +21,7 @@ import torch.nn.functional as F
 from ..parallel.values import Variable, VariableAggregation, VariableSynchronization, create_variable
 from ..ops import conv as _conv
 from ..ops import conv_f32 as _conv_f32
+from ..ops import grouped_conv as _gconv
 from ..ops import dense as _dense
 from ..ops import depthwise as _dw
 from . import activations as _act
@@ -468,6 +469,28 @@ class Conv2D(Layer):
                                                          anchor=anchor, act=act, gb_out=gb))
             y = _conv_f32.conv2d(x, wv, b, self.strides, pads, self.dilation_rate, grad_out=gt, anchor=anchor, act=act,
                                  gb_out=gb)
+            return y if act else self.activation(y)
+        if (self.groups > 1 and x.is_cuda and not _gconv.use_torch() and _conv.mode() != "miopen"
+                and (_gconv.supported(x, self.kernel.value, self.groups)
+                     or (x.dtype in (torch.float16, torch.float64) and _gconv._shape_ok(x, self.kernel.value, self.groups)))):
+            # grouped layers: per-group implicit GEMMs on the MFMA (ops/grouped_conv.py); the f32 master kernel
+            # and bias are read as they are, dW / db go straight into the slab
+            pads = (0, 0, 0, 0)
+            if self.padding == "same":
+                ph = _same_pads(x.shape[1], self.kernel_size[0], self.strides[0], self.dilation_rate[0])
+                pw = _same_pads(x.shape[2], self.kernel_size[1], self.strides[1], self.dilation_rate[1])
+                pads = (ph[0], ph[1], pw[0], pw[1])
+            gt = self.kernel.grad_target()
+            gb, bv = None, (self.bias.value if (self.bias is not None and not _fold_bias) else None)
+            if gt is not None and gt.is_contiguous():
+                anchor = self.kernel.value
+                if bv is not None:
+                    gb = self.bias.grad_target()
+            else:
+                gt, anchor = None, None
+            act = _fused_act(self.activation)
+            y = _gconv.conv2d(x, self.kernel.value, bv, self.groups, self.strides, pads, self.dilation_rate,
+                              grad_out=gt, anchor=anchor, act=act, gb_out=gb)
             return y if act else self.activation(y)
         if x.is_cuda:  # no hand-written kernel covers this conv: library path, counted (ops/conv.py)
             _conv._lib("conv2d", f"{str(x.dtype).replace('torch.', '')} C={x.shape[-1]} K={w.shape[0]} "

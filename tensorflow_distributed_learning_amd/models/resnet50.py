@@ -20,16 +20,18 @@ def _norm(L, name, bn_kw):
     return L.BatchNormalization(axis=3, epsilon=1.001e-5, name=name, **bn_kw)
 
 
-def _block(x, filters, L, stride=1, conv_shortcut=True, name="", bn_kw=None):
+def _block(x, filters, L, stride=1, conv_shortcut=True, name="", bn_kw=None, groups=1, width_per_group=64):
+    # the bottleneck's inner width: filters for ResNet, filters * width_per_group * groups / 64 for ResNeXt
+    inner = filters * width_per_group * groups // 64
     if conv_shortcut:
         sc = L.Conv2D(4 * filters, 1, strides=stride, name=name + "_0_conv")(x)
         sc = _norm(L, name + "_0_bn", bn_kw)(sc)
     else:
         sc = x
-    x = L.Conv2D(filters, 1, strides=stride, name=name + "_1_conv")(x)
+    x = L.Conv2D(inner, 1, strides=stride, name=name + "_1_conv")(x)
     x = _norm(L, name + "_1_bn", bn_kw)(x)
     x = L.Activation("relu", name=name + "_1_relu")(x)
-    x = L.Conv2D(filters, 3, padding="same", name=name + "_2_conv")(x)
+    x = L.Conv2D(inner, 3, padding="same", name=name + "_2_conv", **({"groups": groups} if groups != 1 else {}))(x)
     x = _norm(L, name + "_2_bn", bn_kw)(x)
     x = L.Activation("relu", name=name + "_2_relu")(x)
     x = L.Conv2D(4 * filters, 1, name=name + "_3_conv")(x)
@@ -38,17 +40,21 @@ def _block(x, filters, L, stride=1, conv_shortcut=True, name="", bn_kw=None):
     return L.Activation("relu", name=name + "_out")(x)
 
 
-def _stack(x, filters, blocks, L, stride1=2, name="", bn_kw=None):
-    x = _block(x, filters, L, stride=stride1, name=name + "_block1", bn_kw=bn_kw)
+def _stack(x, filters, blocks, L, stride1=2, name="", bn_kw=None, **gw):
+    x = _block(x, filters, L, stride=stride1, name=name + "_block1", bn_kw=bn_kw, **gw)
     for i in range(2, blocks + 1):
-        x = _block(x, filters, L, conv_shortcut=False, name=name + "_block" + str(i), bn_kw=bn_kw)
+        x = _block(x, filters, L, conv_shortcut=False, name=name + "_block" + str(i), bn_kw=bn_kw, **gw)
     return x
 
 
 def ResNet50(include_top: bool = True, weights=None, input_tensor=None, input_shape=None, pooling=None,  # noqa: N802
              classes: int = 1000, classifier_activation: Optional[str] = "softmax", keras_module=None,
-             synchronized_batch_norm: bool = False, norm: str = "batch", norm_groups: int = 32, **kw):
-    """``synchronized_batch_norm``: every BatchNormalization with ``synchronized=True`` (training statistics
+             synchronized_batch_norm: bool = False, norm: str = "batch", norm_groups: int = 32, groups: int = 1,
+             width_per_group: int = 64, **kw):
+    """``groups`` / ``width_per_group``: the 3x3 convolution of every bottleneck becomes a grouped convolution over
+    an inner width of ``filters * width_per_group * groups / 64`` (``groups=32, width_per_group=4``: ResNeXt-50
+    32x4d); the defaults build ResNet-50 itself.
+    ``synchronized_batch_norm``: every BatchNormalization with ``synchronized=True`` (training statistics
     over the global batch of all replicas; not a tf.keras.applications argument).
     ``norm="group"``: every BatchNormalization replaced by ``GroupNormalization(norm_groups)`` under the
     same layer names (per-sample statistics: no moving averages, nothing to synchronize)."""
@@ -56,6 +62,10 @@ def ResNet50(include_top: bool = True, weights=None, input_tensor=None, input_sh
         raise ValueError(f"ResNet50: norm must be 'batch' or 'group', got {norm!r}")
     if norm == "group" and synchronized_batch_norm:
         raise ValueError("ResNet50: synchronized_batch_norm applies to norm='batch' only")
+    groups, width_per_group = int(groups), int(width_per_group)
+    if groups < 1 or width_per_group < 1:
+        raise ValueError("ResNet50: groups and width_per_group must be positive")
+    gw = {"groups": groups, "width_per_group": width_per_group}
     if weights not in (None, "none"):
         raise ValueError("pretrained weights are not available offline; use weights=None")
     if keras_module is None:
@@ -71,10 +81,10 @@ def ResNet50(include_top: bool = True, weights=None, input_tensor=None, input_sh
     x = L.Activation("relu", name="conv1_relu")(x)
     x = L.ZeroPadding2D(padding=((1, 1), (1, 1)), name="pool1_pad")(x)
     x = L.MaxPooling2D(3, strides=2, name="pool1_pool")(x)
-    x = _stack(x, 64, 3, L, stride1=1, name="conv2", bn_kw=bn_kw)
-    x = _stack(x, 128, 4, L, name="conv3", bn_kw=bn_kw)
-    x = _stack(x, 256, 6, L, name="conv4", bn_kw=bn_kw)
-    x = _stack(x, 512, 3, L, name="conv5", bn_kw=bn_kw)
+    x = _stack(x, 64, 3, L, stride1=1, name="conv2", bn_kw=bn_kw, **gw)
+    x = _stack(x, 128, 4, L, name="conv3", bn_kw=bn_kw, **gw)
+    x = _stack(x, 256, 6, L, name="conv4", bn_kw=bn_kw, **gw)
+    x = _stack(x, 512, 3, L, name="conv5", bn_kw=bn_kw, **gw)
     if include_top:
         x = L.GlobalAveragePooling2D(name="avg_pool")(x)
         x = L.Dense(classes, activation=classifier_activation, name="predictions")(x)
