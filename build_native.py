@@ -42,6 +42,8 @@ HIP_FILE_FLAGS = {
     "depthwise.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # grouped_conv.hip: the same for its epilogue and its fixed-order partial-sum adds
     "grouped_conv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # conv_transpose.hip: the same
+    "conv_transpose.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

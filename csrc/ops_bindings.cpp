@@ -17,6 +17,7 @@
 #include "kernels/groupnorm.h"
 #include "kernels/depthwise.h"
 #include "kernels/grouped_conv.h"
+#include "kernels/conv_transpose.h"
 #include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
@@ -1803,6 +1804,120 @@ std::map<std::string, int64_t> gconv_plan(std::vector<int64_t> x_shape, int64_t 
   m["wgrad_mfma"] = p.wmfma;
   return m;
 }
+// ---- transposed convolution (kernels/conv_transpose.h): x [N,H,W,C], w f32 [kh,kw,F,C], y [N,OH,OW,F]
+// geo = (sh, sw, dh, dw, pt, pl)
+struct CtShape {
+  tdl::CtGeom g;
+  tdl::CtPlan plan;
+};
+// the limits ops/conv_transpose.py's supported() mirrors
+CtShape ct_check(at::IntArrayRef xs, int64_t F, int64_t kh, int64_t kw, int64_t OH, int64_t OW,
+                 const std::vector<int64_t>& geo, const char* what) {
+  TORCH_CHECK(xs.size() == 4 && geo.size() == 6, what, ": a [N,H,W,C] shape and (sh, sw, dh, dw, pt, pl) expected");
+  for (int64_t v : xs) TORCH_CHECK(v >= 1 && v < (int64_t(1) << 31), what, ": bad input shape");
+  TORCH_CHECK(F >= 1 && kh >= 1 && kw >= 1 && kh * kw * std::max(xs[3], F) <= tdl::kCtMaxRed, what,
+              ": kh * kw * max(C, F) <= 2^20 expected");
+  TORCH_CHECK(geo[0] >= 1 && geo[1] >= 1 && geo[0] <= tdl::kCtMaxStride && geo[1] <= tdl::kCtMaxStride, what,
+              ": strides 1 .. 8 expected");
+  for (int i = 2; i < 6; ++i)
+    TORCH_CHECK(geo[i] >= (i < 4 ? 1 : 0) && geo[i] < 65536, what, ": dilations >= 1 and pads >= 0, below 65536");
+  TORCH_CHECK(OH >= 1 && OW >= 1 && OH < (int64_t(1) << 28) && OW < (int64_t(1) << 28), what, ": bad output size");
+  TORCH_CHECK((xs[1] - 1) * geo[0] + (kh - 1) * geo[2] < (int64_t(1) << 28) &&
+                  (xs[2] - 1) * geo[1] + (kw - 1) * geo[3] < (int64_t(1) << 28), what, ": window extent of 2^28 or more");
+  TORCH_CHECK(xs[0] * xs[1] * xs[2] * xs[3] < (int64_t(1) << 31) && xs[0] * OH * OW * F < (int64_t(1) << 31) &&
+                  kh * kw * F * xs[3] < (int64_t(1) << 31), what, ": 2^31 elements or more");
+  CtShape sh;
+  sh.g = tdl::CtGeom{(int)xs[0], (int)xs[1], (int)xs[2], (int)xs[3], (int)F, (int)OH, (int)OW, (int)kh, (int)kw,
+                     (int)geo[0], (int)geo[1], (int)geo[2], (int)geo[3], (int)geo[4], (int)geo[5]};
+  sh.plan = tdl::convt_plan(sh.g);
+  TORCH_CHECK(sh.plan.wcoltiles < 65536 && sh.plan.ws_elems < (int64_t(1) << 31), what,
+              ": too many column tiles or too large a weight-gradient workspace");
+  return sh;
+}
+tdl::CtDType ct_dtype(const at::Tensor& t) { return t.scalar_type() == at::kBFloat16 ? tdl::CtDType::kBF16 : tdl::CtDType::kF32; }
+const float* ct_weight(const at::Tensor& w, const char* what) {
+  const float* p = dw_f32(w, w.numel(), what, "w");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(p) % 16 == 0, what, ": w must be 16-byte aligned");
+  return p;
+}
+
+at::Tensor convt_forward(at::Tensor x, at::Tensor w, c10::optional<at::Tensor> bias, std::vector<int64_t> geo,
+                         int64_t OH, int64_t OW, int64_t act) {
+  const char* what = "conv2d_transpose";
+  dw_data(x, what, "x");
+  TORCH_CHECK(w.dim() == 4 && w.size(3) == x.size(3), what, ": w must be [kh,kw,F,C]");
+  const CtShape sh = ct_check(x.sizes(), w.size(2), w.size(0), w.size(1), OH, OW, geo, what);
+  const float* pw = ct_weight(w, what);
+  const float* pb = dw_f32(bias, w.size(2), what, "bias");
+  TORCH_CHECK(act == 0 || act == 1, what, ": act 0 (none) or 1 (ReLU)");
+  auto y = fresh({x.size(0), OH, OW, w.size(2)}, x.options());
+  tdl::convt_forward(x.data_ptr(), pw, pb, y.data_ptr(), ct_dtype(x), sh.g, (int)act, cur_stream());
+  return y;
+}
+
+at::Tensor convt_dgrad(at::Tensor dy, at::Tensor w, int64_t H, int64_t W, std::vector<int64_t> geo,
+                       c10::optional<at::Tensor> dy_mask) {
+  const char* what = "conv2d_transpose dgrad";
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(w.dim() == 4 && w.size(2) == dy.size(3), what, ": w must be [kh,kw,F,C], dy [N,OH,OW,F]");
+  const std::vector<int64_t> xs{dy.size(0), H, W, w.size(3)};
+  const CtShape sh = ct_check(xs, w.size(2), w.size(0), w.size(1), dy.size(1), dy.size(2), geo, what);
+  const float* pw = ct_weight(w, what);
+  const void* pm = gc_mask(dy_mask, dy, what);
+  auto dx = fresh(xs, dy.options());
+  tdl::convt_dgrad(dy.data_ptr(), pm, pw, dx.data_ptr(), ct_dtype(dy), sh.g, cur_stream());
+  return dx;
+}
+
+// dW f32 [kh,kw,F,C] (out, added into when accumulate); dbias f32 [F]: written, or added into when accumulate
+at::Tensor convt_wgrad(at::Tensor x, at::Tensor dy, int64_t kh, int64_t kw, std::vector<int64_t> geo,
+                       c10::optional<at::Tensor> dy_mask, c10::optional<at::Tensor> out, bool accumulate,
+                       c10::optional<at::Tensor> dbias) {
+  const char* what = "conv2d_transpose wgrad";
+  dw_data(x, what, "x");
+  dw_data(dy, what, "dy");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.size(0) == x.size(0), what, ": x and dy of one dtype and batch");
+  const int64_t F = dy.size(3), C = x.size(3);
+  const CtShape sh = ct_check(x.sizes(), F, kh, kw, dy.size(1), dy.size(2), geo, what);
+  const void* pm = gc_mask(dy_mask, dy, what);
+  auto f = x.options().dtype(at::kFloat);
+  const bool given = out.has_value() && out->defined();
+  at::Tensor dW = given ? *out : fresh({kh, kw, F, C}, f);
+  float* pw = const_cast<float*>(dw_f32(dW, kh * kw * F * C, what, "out"));
+  float* pb = const_cast<float*>(dw_f32(dbias, F, what, "dbias"));
+  auto ws = fresh({sh.plan.ws_elems}, f);
+  tdl::convt_wgrad(x.data_ptr(), dy.data_ptr(), pm, ws.data_ptr<float>(), pw, pb, accumulate && given ? 1 : 0,
+                   ct_dtype(x), sh.g, cur_stream());
+  return dW;
+}
+
+pybind11::dict convt_plan(std::vector<int64_t> x_shape, int64_t F, int64_t kh, int64_t kw, int64_t OH, int64_t OW,
+                          std::vector<int64_t> geo) {
+  const tdl::CtPlan p = ct_check(x_shape, F, kh, kw, OH, OW, geo, "conv2d_transpose plan").plan;
+  pybind11::dict m;
+  auto pass = [&](const std::string& n, const tdl::CtPass& q) {
+    m[pybind11::str(n + "_vec")] = q.vec;
+    m[pybind11::str(n + "_tiles")] = q.tiles;
+    m[pybind11::str(n + "_colblocks")] = q.colblocks;
+    m[pybind11::str(n + "_pixels_per_tile")] = q.ptile;
+    m[pybind11::str(n + "_pixel_tiles")] = q.ptiles;
+    m[pybind11::str(n + "_kchunks")] = q.kchunks;
+    m[pybind11::str(n + "_mfma")] = q.mfma;
+  };
+  m["phases"] = p.phases;
+  m["phase_taps"] = std::vector<int64_t>(p.phase_taps, p.phase_taps + p.phases);
+  m["empty_phases"] = p.empty_phases;
+  pass("fwd", p.fwd);
+  pass("dgrad", p.dgrad);
+  m["wgrad_rowtiles"] = p.wrowtiles;
+  m["wgrad_itemblocks"] = p.witemblocks;
+  m["wgrad_coltiles"] = p.wcoltiles;
+  m["wgrad_chunk"] = p.wchunk;
+  m["wgrad_splits"] = p.wsplits;
+  m["wgrad_mfma"] = p.wmfma;
+  m["workspace_elems"] = p.ws_elems;
+  return m;
+}
 }  // namespace
 
 void register_ops(pybind11::module& m) {
@@ -1846,6 +1961,20 @@ void register_ops(pybind11::module& m) {
   m.def("gconv_plan", &gconv_plan, "grouped convolution plan as a dict (raises for a shape outside the kernels' "
         "limits); no GPU needed", pybind11::arg("x_shape"), pybind11::arg("filters"), pybind11::arg("groups"),
         pybind11::arg("kh"), pybind11::arg("kw"), pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("geo"));
+  m.def("convt_forward", &convt_forward, "channels-last transposed convolution forward (+ bias, + ReLU): y",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("geo"), pybind11::arg("out_h"),
+        pybind11::arg("out_w"), pybind11::arg("act") = 0);
+  m.def("convt_dgrad", &convt_dgrad, "channels-last transposed convolution input gradient: dx; dy_mask: dy where "
+        "mask > 0", pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("in_h"), pybind11::arg("in_w"),
+        pybind11::arg("geo"), pybind11::arg("dy_mask") = pybind11::none());
+  m.def("convt_wgrad", &convt_wgrad, "channels-last transposed convolution weight (+ bias) gradient, deterministic "
+        "split reduction: dW [kh,kw,F,C]", pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("kh"),
+        pybind11::arg("kw"), pybind11::arg("geo"), pybind11::arg("dy_mask") = pybind11::none(),
+        pybind11::arg("out") = pybind11::none(), pybind11::arg("accumulate") = false,
+        pybind11::arg("dbias") = pybind11::none());
+  m.def("convt_plan", &convt_plan, "transposed convolution plan as a dict (raises for a shape outside the kernels' "
+        "limits); no GPU needed", pybind11::arg("x_shape"), pybind11::arg("filters"), pybind11::arg("kh"),
+        pybind11::arg("kw"), pybind11::arg("out_h"), pybind11::arg("out_w"), pybind11::arg("geo"));
   m.def("xent_fwd", &xent_fwd, "sparse softmax cross-entropy forward: (loss, logsumexp)");
   m.def("xent_bwd", &xent_bwd, "sparse softmax cross-entropy backward: (softmax - onehot) * g");
   m.def("xent_head", &xent_head, "fused loss head: mean-reduced sparse softmax cross-entropy, its dlogits and "

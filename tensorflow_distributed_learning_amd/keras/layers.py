@@ -22,6 +22,7 @@ from ..parallel.values import Variable, VariableAggregation, VariableSynchroniza
 from ..ops import conv as _conv
 from ..ops import conv_f32 as _conv_f32
 from ..ops import grouped_conv as _gconv
+from ..ops import conv_transpose as _convt
 from ..ops import dense as _dense
 from ..ops import depthwise as _dw
 from . import activations as _act
@@ -669,6 +670,89 @@ class SeparableConv2D(DepthwiseConv2D):
     def get_config(self):
         return dict(super().get_config(), filters=self.filters,
                     pointwise_initializer=_init.serialize(self.pointwise_initializer))
+
+
+class Conv2DTranspose(Layer):
+    """tf.keras.layers.Conv2DTranspose, channels_last: the learned upsampler of decoders and generators.  Weights:
+    ``kernel [kh, kw, filters, C]`` (Keras' layout: filters before input channels) and ``bias [filters]``.  On the
+    GPU it runs on the stride-phase implicit-GEMM kernels (ops/conv_transpose.py, which states the size and crop
+    rules) in f32 or bf16 (``mixed_bfloat16``); the kernel and bias stay f32 there.  Not a Conv2D: the Conv2D
+    fusions of keras/fusion.py do not apply to it."""
+
+    def __init__(self, filters, kernel_size, strides=(1, 1), padding="valid", output_padding=None, data_format=None,
+                 dilation_rate=(1, 1), activation=None, use_bias=True, kernel_initializer="glorot_uniform",
+                 bias_initializer="zeros", kernel_regularizer=None, bias_regularizer=None, activity_regularizer=None,
+                 kernel_constraint=None, bias_constraint=None, **kw):
+        super().__init__(**kw)
+        if data_format not in (None, "channels_last"):
+            raise ValueError("only channels_last (NHWC) is supported – the TF default")
+        if kernel_constraint is not None or bias_constraint is not None:
+            raise ValueError("Conv2DTranspose: constraints are not implemented")
+        self.filters = int(filters)
+        self.kernel_size = _pair(kernel_size)
+        self.strides = _pair(strides)
+        self.padding = padding.lower()
+        if self.padding not in ("valid", "same"):
+            raise ValueError(f"padding must be 'valid' or 'same', got {padding!r}")
+        self.output_padding = _pair(output_padding) if output_padding is not None else None
+        if self.output_padding is not None and any(not 0 <= p < s for p, s in zip(self.output_padding, self.strides)):
+            raise ValueError(f"output_padding {self.output_padding} must be >= 0 and below the strides {self.strides}")
+        self.dilation_rate = _pair(dilation_rate)
+        self.activation = _act.get(activation)
+        self.use_bias = use_bias
+        self.kernel_initializer = _init.get(kernel_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        self.kernel_regularizer = _regularizer_from(kernel_regularizer)
+        self.bias_regularizer = _regularizer_from(bias_regularizer)
+
+    def build(self, input_shape):
+        kh, kw = self.kernel_size
+        self.kernel = self.add_weight("kernel", (kh, kw, self.filters, int(input_shape[-1])),
+                                      initializer=self.kernel_initializer, regularizer=self.kernel_regularizer)
+        self.bias = self.add_weight("bias", (self.filters,), initializer=self.bias_initializer,
+                                    regularizer=self.bias_regularizer) if self.use_bias else None
+        self.built = True
+
+    def call(self, x, training=None):
+        x = _autocast_input(x)
+        act = _fused_act(self.activation)  # ReLU in the forward epilogue and the backward masks
+        k, b = self.kernel, self.bias
+        gt = None
+        if self.trainable and not _convt.use_torch() and _convt.supported(x, k.value, self.strides, self.padding,
+                                                                          self.output_padding, self.dilation_rate):
+            gt = k.grad_target()
+        gb = b.grad_target() if (b is not None and gt is not None) else None
+        if gt is not None and gt.is_contiguous() and (b is None or gb is not None):
+            # kernel / bias gradients go straight into the trainer's slab
+            y = _convt.conv2d_transpose(x, k.value.detach(), b.value.detach() if b is not None else None, self.strides,
+                                        self.padding, self.output_padding, self.dilation_rate, grad_out=gt,
+                                        anchor=k.value, act=act, gb_out=gb)
+        else:
+            y = _convt.conv2d_transpose(x, k.value, b.value if b is not None else None, self.strides, self.padding,
+                                        self.output_padding, self.dilation_rate, act=act)
+        return y if act else self.activation(y)
+
+    def compute_output_shape(self, s):
+        op = self.output_padding if self.output_padding is not None else (None, None)
+        hw = tuple(None if s[1 + a] is None else
+                   _convt.out_size(s[1 + a], self.kernel_size[a], self.strides[a], self.dilation_rate[a], self.padding,
+                                   op[a])[0] for a in (0, 1))
+        return (s[0],) + hw + (self.filters,)
+
+    def get_config(self):
+        cfg = dict(super().get_config(), filters=self.filters, kernel_size=list(self.kernel_size),
+                   strides=list(self.strides), padding=self.padding,
+                   output_padding=list(self.output_padding) if self.output_padding is not None else None,
+                   dilation_rate=list(self.dilation_rate), activation=_act.serialize(self.activation),
+                   use_bias=self.use_bias, kernel_initializer=_init.serialize(self.kernel_initializer),
+                   bias_initializer=_init.serialize(self.bias_initializer))
+        for k in ("kernel_regularizer", "bias_regularizer"):  # (only when set)
+            if getattr(self, k) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
+
+
+Convolution2DTranspose = Conv2DTranspose
 
 
 class _Pooled:
@@ -1527,10 +1611,10 @@ def multiply(inputs, **kw):
 
 
 LAYER_CLASSES = {c.__name__: c for c in (
-    InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
+    InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
     SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
-__all__ = sorted(LAYER_CLASSES) + ["Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]
+__all__ = sorted(LAYER_CLASSES) + ["Convolution2DTranspose", "Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]
