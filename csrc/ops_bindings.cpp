@@ -18,6 +18,7 @@
 #include "kernels/depthwise.h"
 #include "kernels/grouped_conv.h"
 #include "kernels/conv_transpose.h"
+#include "kernels/attention.h"
 #include "kernels/loss_head.h"
 #include "kernels/ops.h"
 #include "kernels/pool.h"
@@ -1918,9 +1919,120 @@ pybind11::dict convt_plan(std::vector<int64_t> x_shape, int64_t F, int64_t kh, i
   m["workspace_elems"] = p.ws_elems;
   return m;
 }
+// ---- fused attention (kernels/attention.h): q [B,T,H,D], k [B,S,H,D], v [B,S,H,Dv] strided views, mask bytes
+// [B,T,S] or [B,H,T,S].  The limits ops/attention.py's supported() mirrors.
+void attn_operand(const at::Tensor& t, const at::Tensor& like, int64_t* strides, const char* what, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.scalar_type() == like.scalar_type(), what, ": ", name,
+              " must be a 4-D GPU tensor of q's dtype");
+  TORCH_CHECK(t.numel() >= 1 && t.numel() < (int64_t(1) << 31), what, ": ", name, " must hold 1 .. 2^31 - 1 elements");
+  const int64_t per16 = 16 / t.element_size();
+  int64_t span = 0;
+  for (int i = 0; i < 3; ++i) {
+    TORCH_CHECK(t.stride(i) >= 0 && t.stride(i) % per16 == 0, what, ": ", name, " strides must be multiples of 16 bytes");
+    span += (t.size(i) - 1) * t.stride(i);
+    strides[i] = t.stride(i);
+  }
+  TORCH_CHECK(t.stride(3) == 1 && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 && span < (int64_t(1) << 31), what,
+              ": ", name, " needs a contiguous, 16-byte aligned innermost axis and a span below 2^31 elements");
+}
+tdl::AttnArgs attn_check(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale, bool causal,
+                         const c10::optional<at::Tensor>& mask, const char* what) {
+  TORCH_CHECK(q.scalar_type() == at::kFloat || q.scalar_type() == at::kBFloat16, what, ": f32 or bf16 operands expected");
+  tdl::AttnArgs a{};
+  attn_operand(q, q, a.qs, what, "q");
+  attn_operand(k, q, a.ks, what, "k");
+  attn_operand(v, q, a.vs, what, "v");
+  TORCH_CHECK(k.size(0) == q.size(0) && v.size(0) == q.size(0) && k.size(2) == q.size(2) && v.size(2) == q.size(2) &&
+                  k.size(3) == q.size(3) && v.size(1) == k.size(1), what, ": q [B,T,H,D], k [B,S,H,D], v [B,S,H,Dv] expected");
+  TORCH_CHECK(q.size(0) <= 65535 && q.size(2) <= 65535, what, ": at most 65535 batches and heads");
+  TORCH_CHECK(tdl::attn_head_pad((int)q.size(3), (int)v.size(3)) != 0, what, ": D and Dv must be multiples of 8 up to 128");
+  TORCH_CHECK(q.size(0) * q.size(1) * q.size(2) * v.size(3) < (int64_t(1) << 31), what, ": output of 2^31 elements or more");
+  a.q = q.data_ptr(), a.k = k.data_ptr(), a.v = v.data_ptr();
+  a.B = (int)q.size(0), a.T = (int)q.size(1), a.H = (int)q.size(2), a.D = (int)q.size(3);
+  a.S = (int)k.size(1), a.Dv = (int)v.size(3);
+  a.causal = causal ? 1 : 0;
+  a.scale = (float)scale;
+  if (mask.has_value() && mask->defined()) {
+    const at::Tensor& m = *mask;
+    TORCH_CHECK(m.is_cuda() && (m.scalar_type() == at::kByte || m.scalar_type() == at::kBool) &&
+                    (m.dim() == 3 || m.dim() == 4), what, ": mask must be a uint8 / bool GPU tensor [B,T,S] or [B,H,T,S]");
+    const int o = m.dim() == 4 ? 1 : 0;
+    TORCH_CHECK(m.size(0) == a.B && (!o || m.size(1) == a.H) && m.size(1 + o) == a.T && m.size(2 + o) == a.S, what,
+                ": mask shape does not match");
+    int64_t span = 0;
+    for (int i = 0; i < m.dim(); ++i) {
+      TORCH_CHECK(m.stride(i) >= 0, what, ": negative mask stride");
+      span += (m.size(i) - 1) * m.stride(i);
+    }
+    TORCH_CHECK(span < (int64_t(1) << 31), what, ": mask span of 2^31 bytes or more");
+    a.mask = static_cast<const uint8_t*>(m.data_ptr());
+    a.ms[0] = m.stride(0), a.ms[1] = o ? m.stride(1) : 0, a.ms[2] = m.stride(1 + o), a.ms[3] = m.stride(2 + o);
+  }
+  return a;
+}
+
+// (o [B,T,H,Dv] in q's dtype, lse f32 [B,H,T])
+std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool causal,
+                                     c10::optional<at::Tensor> mask) {
+  tdl::AttnArgs a = attn_check(q, k, v, scale, causal, mask, "attention");
+  auto o = fresh({a.B, a.T, a.H, a.Dv}, q.options());
+  auto lse = fresh({a.B, a.H, a.T}, q.options().dtype(at::kFloat));
+  a.o = o.data_ptr(), a.lse = lse.data_ptr<float>();
+  tdl::attn_forward(a, q.scalar_type() == at::kBFloat16, cur_stream());
+  return {o, lse};
+}
+
+// (dq, dk, dv), contiguous, in q's dtype
+std::vector<at::Tensor> attn_backward(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+                                      at::Tensor dout, double scale, bool causal, c10::optional<at::Tensor> mask) {
+  const char* what = "attention backward";
+  tdl::AttnArgs a = attn_check(q, k, v, scale, causal, mask, what);
+  attn_operand(dout, q, a.gs, what, "do");
+  TORCH_CHECK(o.is_cuda() && o.is_contiguous() && o.scalar_type() == q.scalar_type() &&
+                  o.sizes() == at::IntArrayRef({a.B, a.T, a.H, a.Dv}) && dout.sizes() == o.sizes(), what,
+              ": o must be the forward's contiguous [B,T,H,Dv] output and do of its shape");
+  TORCH_CHECK(lse.is_cuda() && lse.is_contiguous() && lse.scalar_type() == at::kFloat &&
+                  lse.sizes() == at::IntArrayRef({a.B, a.H, a.T}), what, ": lse must be contiguous f32 [B,H,T]");
+  auto dq = fresh({a.B, a.T, a.H, a.D}, q.options(), 2);
+  auto dk = fresh({a.B, a.S, a.H, a.D}, q.options(), 2);
+  auto dv = fresh({a.B, a.S, a.H, a.Dv}, q.options(), 2);
+  auto delta = fresh({a.B, a.H, a.T}, lse.options());
+  a.dout = dout.data_ptr(), a.o = o.data_ptr(), a.lse = lse.data_ptr<float>(), a.delta = delta.data_ptr<float>();
+  a.dq = dq.data_ptr(), a.dk = dk.data_ptr(), a.dv = dv.data_ptr();
+  tdl::attn_backward(a, q.scalar_type() == at::kBFloat16, cur_stream());
+  return {dq, dk, dv};
+}
+
+pybind11::dict attn_plan(int64_t B, int64_t H, int64_t T, int64_t S, int64_t D, int64_t Dv, bool bf16, bool causal) {
+  TORCH_CHECK(B >= 1 && H >= 1 && T >= 1 && S >= 1 && B <= 65535 && H <= 65535 && T < (int64_t(1) << 31) &&
+                  S < (int64_t(1) << 31) && tdl::attn_head_pad((int)D, (int)Dv) != 0,
+              "attention plan: shape outside the kernels' limits");
+  const tdl::AttnPlan p = tdl::attn_plan((int)B, (int)H, (int)T, (int)S, (int)D, (int)Dv, bf16, causal);
+  pybind11::dict m;
+  m["head_pad"] = p.hd;
+  m["q_tiles"] = p.q_tiles;
+  m["k_tiles"] = p.k_tiles;
+  m["causal_skipped"] = p.causal_skipped;
+  m["staging"] = "single";  // every variant keeps one tile per operand resident (kernels/attention.h)
+  m["lds_fwd"] = p.lds_fwd;
+  m["lds_dq"] = p.lds_dq;
+  m["lds_dkv"] = p.lds_dkv;
+  m["mfma_fwd"] = p.mfma_fwd;
+  m["mfma_bwd"] = p.mfma_bwd;
+  return m;
+}
 }  // namespace
 
 void register_ops(pybind11::module& m) {
+  m.def("attn_forward", &attn_forward, "fused scaled-dot-product attention forward over strided [B,T,H,D] views: (o, lse)",
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),
+        pybind11::arg("mask") = pybind11::none());
+  m.def("attn_backward", &attn_backward, "fused attention backward (delta, dQ, dK/dV kernels; no atomics): (dq, dk, dv)",
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
+        pybind11::arg("do"), pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("mask") = pybind11::none());
+  m.def("attn_plan", &attn_plan, "fused attention plan as a dict (raises outside the kernels' limits); no GPU needed",
+        pybind11::arg("B"), pybind11::arg("H"), pybind11::arg("T"), pybind11::arg("S"), pybind11::arg("D"),
+        pybind11::arg("Dv"), pybind11::arg("bf16"), pybind11::arg("causal"));
   m.def("gn_forward", &gn_forward, "channels-last group normalisation forward: (y, stats, part, coef)",
         pybind11::arg("x"), pybind11::arg("groups"), pybind11::arg("gamma"), pybind11::arg("beta"),
         pybind11::arg("eps"), pybind11::arg("phases") = 7, pybind11::arg("ws") = pybind11::none());

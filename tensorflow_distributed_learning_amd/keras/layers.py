@@ -23,6 +23,7 @@ from ..ops import conv as _conv
 from ..ops import conv_f32 as _conv_f32
 from ..ops import grouped_conv as _gconv
 from ..ops import conv_transpose as _convt
+from ..ops import attention as _attn
 from ..ops import dense as _dense
 from ..ops import depthwise as _dw
 from . import activations as _act
@@ -260,40 +261,7 @@ class Dense(Layer):
         self.built = True
 
     def call(self, x, training=None):
-        x = _autocast_input(x)
-        if _dense.dense_supported(x, self.units):
-            # bf16 on the GPU: hand-written MFMA GEMMs (ops/dense.py), gradients straight into the
-            # trainer's slab when it is bound
-            gw = self.kernel.grad_target()
-            gb = self.bias.grad_target() if self.bias is not None else None
-            if gw is not None and (self.bias is None or gb is not None):
-                w = self.kernel.compute_view(x.dtype)
-                w = w if w is not None else self.kernel.value.detach().to(x.dtype)
-                b = self.bias.value.detach() if self.bias is not None else None
-                return self.activation(_dense.dense_bf16(x, w, b, (gw, gb), anchor=self.kernel.value))
-            b = self.bias.value if self.bias is not None else None
-            return self.activation(_dense.dense_bf16(x, self.kernel.cast(x.dtype), b))
-        low = x.is_cuda and x.dtype == torch.bfloat16 and self.kernel.value.dtype == torch.float32
-        if (_conv_f32.dense_supported(x) or low) and self.kernel.value.dtype == torch.float32:
-            # f32 on the GPU: the f32-MFMA GEMM of csrc/kernels/gemm_f32.hip (no hipBLASLt); also a bf16
-            # input whose shape the bf16 GEMM does not tile (a 10-class head under mixed_bfloat16):
-            # f32 math on the f32 master weights, bf16 out (the layer's compute dtype)
-            xf = x.float() if low else x
-            gw = self.kernel.grad_target()
-            gb = self.bias.grad_target() if self.bias is not None else None
-            act = _fused_act(self.activation)  # ReLU inside the GEMMs (forward epilogue, backward masks)
-            if gw is not None and gw.is_contiguous() and (self.bias is None or gb is not None):
-                b = self.bias.value.detach() if self.bias is not None else None
-                y = _conv_f32.dense(xf, self.kernel.value.detach(), b, (gw, gb), anchor=self.kernel.value, act=act)
-            else:
-                b = self.bias.value if self.bias is not None else None
-                y = _conv_f32.dense(xf, self.kernel.value, b, act=act)
-            y = y.to(torch.bfloat16) if low else y
-            return y if act else self.activation(y)
-        y = torch.matmul(x, self.kernel.cast(x.dtype))
-        if self.bias is not None:
-            y = y + self.bias.value.to(y.dtype)
-        return self.activation(y)
+        return _dense_rows(x, self.kernel, self.bias, self.units, self.activation)
 
     def compute_output_shape(self, s):
         return tuple(s[:-1]) + (self.units,)
@@ -302,6 +270,56 @@ class Dense(Layer):
         return dict(super().get_config(), units=self.units, activation=_act.serialize(self.activation),
                     use_bias=self.use_bias, kernel_initializer=_init.serialize(self.kernel_initializer),
                     bias_initializer=_init.serialize(self.bias_initializer))
+
+
+def _dense_rows(x, kernel, bias, units, activation, kshape=None):
+    """``activation(x @ kernel + bias)`` over the rows of ``x [..., d]``: the dispatch of Dense.call.  ``kshape``: the
+    2-D shape ``(d, units)`` in which a kernel variable stored with more axes (MultiHeadAttention's ``[dim,H,D]``),
+    its gradient target and its bias are viewed; None for a kernel that is 2-D already."""
+    def k2(t):  # a kernel-shaped tensor viewed 2-D (a gradient target that cannot be viewed: None)
+        if t is None or kshape is None:
+            return t
+        return t.view(kshape) if t.is_contiguous() else None
+
+    def b1(t):
+        if t is None or kshape is None:
+            return t
+        return t.view(-1) if t.is_contiguous() else None
+
+    x = _autocast_input(x)
+    if _dense.dense_supported(x, units):
+        # bf16 on the GPU: hand-written MFMA GEMMs (ops/dense.py), gradients straight into the
+        # trainer's slab when it is bound
+        gw = k2(kernel.grad_target())
+        gb = b1(bias.grad_target()) if bias is not None else None
+        if gw is not None and (bias is None or gb is not None):
+            w = kernel.compute_view(x.dtype)
+            w = k2(w) if w is not None else k2(kernel.value.detach()).to(x.dtype)
+            b = b1(bias.value.detach()) if bias is not None else None
+            return activation(_dense.dense_bf16(x, w, b, (gw, gb), anchor=kernel.value))
+        b = b1(bias.value) if bias is not None else None
+        return activation(_dense.dense_bf16(x, kernel.cast(x.dtype).reshape(kshape or kernel.shape), b))
+    low = x.is_cuda and x.dtype == torch.bfloat16 and kernel.value.dtype == torch.float32
+    if (_conv_f32.dense_supported(x) or low) and kernel.value.dtype == torch.float32:
+        # f32 on the GPU: the f32-MFMA GEMM of csrc/kernels/gemm_f32.hip (no hipBLASLt); also a bf16
+        # input whose shape the bf16 GEMM does not tile (a 10-class head under mixed_bfloat16):
+        # f32 math on the f32 master weights, bf16 out (the layer's compute dtype)
+        xf = x.float() if low else x
+        gw = k2(kernel.grad_target())
+        gb = b1(bias.grad_target()) if bias is not None else None
+        act = _fused_act(activation)  # ReLU inside the GEMMs (forward epilogue, backward masks)
+        if gw is not None and gw.is_contiguous() and (bias is None or gb is not None):
+            b = b1(bias.value.detach()) if bias is not None else None
+            y = _conv_f32.dense(xf, k2(kernel.value.detach()), b, (gw, gb), anchor=kernel.value, act=act)
+        else:
+            b = b1(bias.value) if bias is not None else None
+            y = _conv_f32.dense(xf, k2(kernel.value), b, act=act)
+        y = y.to(torch.bfloat16) if low else y
+        return y if act else activation(y)
+    y = torch.matmul(x, kernel.cast(x.dtype).reshape(kshape or kernel.shape))
+    if bias is not None:
+        y = y + b1(bias.value).to(y.dtype)
+    return activation(y)
 
 
 def _fused_act(fn) -> int:
@@ -1534,6 +1552,111 @@ class Embedding(Layer):
         return tuple(s) + (self.output_dim,)
 
 
+class MultiHeadAttention(Layer):
+    """tf.keras.layers.MultiHeadAttention over rank-3 inputs: ``layer(query [B,T,dim], value [B,S,dim'], key=None,
+    attention_mask=None [B,T,S], use_causal_mask=False, return_attention_scores=False)``.  Weights, with Keras' names
+    and shapes: ``query/kernel [dim,H,D]``, ``query/bias [H,D]``, the same for ``key``, ``value/kernel [dim',H,Dv]``,
+    ``value/bias [H,Dv]``, ``attention_output/kernel [H,Dv,out]``, ``attention_output/bias [out]``.
+
+    The four projections run through Dense's dispatch (the f32 / bf16 MFMA GEMMs on the GPU, gradients straight into
+    the trainer's slab); their outputs reach the fused attention kernels (ops/attention.py) as ``[B,T,H,D]`` views,
+    without a permute.  A query row whose mask admits no key gives the output bias alone (Keras: the projected mean
+    of the values).  Attention dropout in training and ``return_attention_scores`` use the torch formula."""
+
+    def __init__(self, num_heads, key_dim, value_dim=None, dropout=0.0, use_bias=True, output_shape=None,
+                 attention_axes=None, kernel_initializer="glorot_uniform", bias_initializer="zeros",
+                 kernel_regularizer=None, bias_regularizer=None, **kw):
+        super().__init__(**kw)
+        if attention_axes is not None:
+            raise ValueError("MultiHeadAttention: attention_axes other than None is not implemented")
+        self.num_heads, self.key_dim = int(num_heads), int(key_dim)
+        self.value_dim = int(value_dim) if value_dim is not None else self.key_dim
+        self.dropout, self.use_bias = float(dropout), bool(use_bias)
+        if output_shape is not None and not isinstance(output_shape, int):
+            if len(output_shape) != 1:
+                raise ValueError("MultiHeadAttention: output_shape must be None, an int or a 1-tuple")
+            output_shape = int(output_shape[0])
+        self.output_dim = output_shape
+        self.kernel_initializer = _init.get(kernel_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        self.kernel_regularizer = _regularizer_from(kernel_regularizer)
+        self.bias_regularizer = _regularizer_from(bias_regularizer)
+
+    def __call__(self, query, value=None, key=None, attention_mask=None, use_causal_mask=False,
+                 return_attention_scores=False, training=None):
+        """Packs ``[query, value, key(, attention_mask)]`` (``key`` defaults to ``value``) into the one input
+        structure of Layer.__call__; the functional executor calls back with that list and the flags."""
+        inputs = list(query) if value is None else [query, value, value if key is None else key] + (
+            [attention_mask] if attention_mask is not None else [])
+        kw = {}
+        if use_causal_mask:
+            kw["use_causal_mask"] = True
+        if return_attention_scores:
+            if isinstance(inputs[0], KerasTensor):
+                raise NotImplementedError("MultiHeadAttention: return_attention_scores in a functional model")
+            kw["return_attention_scores"] = True
+        return super().__call__(inputs, training=training, **kw)
+
+    def build(self, shapes):
+        qd, vd, kd = int(shapes[0][-1]), int(shapes[1][-1]), int(shapes[2][-1])
+        H, D, Dv = self.num_heads, self.key_dim, self.value_dim
+        out = self.output_dim if self.output_dim is not None else qd
+
+        def pair(name, kshape, bshape):
+            w = self.add_weight(f"{name}/kernel", kshape, initializer=self.kernel_initializer,
+                                regularizer=self.kernel_regularizer)
+            b = self.add_weight(f"{name}/bias", bshape, initializer=self.bias_initializer,
+                                regularizer=self.bias_regularizer) if self.use_bias else None
+            return w, b
+
+        self.q_proj, self.k_proj = pair("query", (qd, H, D), (H, D)), pair("key", (kd, H, D), (H, D))
+        self.v_proj, self.o_proj = pair("value", (vd, H, Dv), (H, Dv)), pair("attention_output", (H, Dv, out), (out,))
+        self.built = True
+
+    def call(self, inputs, training=None, use_causal_mask=False, return_attention_scores=False):
+        q_in, v_in, k_in = inputs[:3]
+        if q_in.dim() != 3 or v_in.dim() != 3 or k_in.dim() != 3:
+            raise ValueError("MultiHeadAttention: rank-3 [batch, sequence, features] inputs expected")
+        mask = inputs[3] if len(inputs) > 3 else None
+        H, D, Dv = self.num_heads, self.key_dim, self.value_dim
+        B, T, S = q_in.shape[0], q_in.shape[1], v_in.shape[1]
+        ident = _act.get(None)
+
+        def project(x, wb, width):
+            w, b = wb
+            return _dense_rows(x, w, b, H * width, ident, (w.shape[0], H * width)).reshape(x.shape[0], x.shape[1], H, width)
+
+        q, k, v = project(q_in, self.q_proj, D), project(k_in, self.k_proj, D), project(v_in, self.v_proj, Dv)
+        if mask is not None:
+            mask = (mask if mask.dtype == torch.bool else mask != 0).expand(B, T, S)
+        scores = None
+        if return_attention_scores or (training and self.dropout > 0):
+            drop = (lambda p: F.dropout(p, self.dropout, True)) if training and self.dropout > 0 else None
+            o = _attn.sdpa_torch(q, k, v, None, use_causal_mask, mask, dropout=drop,
+                                 return_scores=return_attention_scores)
+            if return_attention_scores:
+                o, scores = o
+        else:
+            o = _attn.sdpa(q, k, v, None, use_causal_mask, mask)
+        w, b = self.o_proj
+        y = _dense_rows(o.reshape(B, T, H * Dv), w, b, w.shape[2], ident, (H * Dv, w.shape[2]))
+        return (y, scores) if return_attention_scores else y
+
+    def compute_output_shape(self, shapes):
+        out = self.output_dim if self.output_dim is not None else shapes[0][-1]
+        return tuple(shapes[0][:-1]) + (out,)
+
+    def get_config(self):
+        cfg = dict(super().get_config(), num_heads=self.num_heads, key_dim=self.key_dim, value_dim=self.value_dim,
+                   dropout=self.dropout, use_bias=self.use_bias, output_shape=self.output_dim,
+                   kernel_initializer=_init.serialize(self.kernel_initializer),
+                   bias_initializer=_init.serialize(self.bias_initializer))
+        for k in ("kernel_regularizer", "bias_regularizer"):  # (only when set, as the other layers' configs)
+            if getattr(self, k) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
+
+
 class _Merge(Layer):
     def compute_output_shape(self, shapes):
         return shapes[0]
@@ -1614,7 +1737,7 @@ LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
-    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, MultiHeadAttention, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
 __all__ = sorted(LAYER_CLASSES) + ["Convolution2DTranspose", "Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]
