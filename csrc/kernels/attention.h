@@ -30,6 +30,21 @@
 // No atomics; every sum's order is fixed by the shape: bit-identical from run to run.  All staging is single
 // (one tile resident): at HD = 128 in f32 the dK/dV kernel's four operand tiles and strip take 155,136 B of the
 // 160 KiB LDS.
+//
+// Attention dropout (the DROP instantiations of the three tile kernels; state or ticket_in set).  With the keep mask
+// z and c = 1 / (1 - rate):  P~ = c z P (rounded once to bf16 for bf16 operands), o = P~ V; the row maximum, the row
+// sum and lse stay those of the undropped row.  Backward: delta = sum_d do o as before (= sum_j P~ dP~), dP~ = dO V^T,
+// dS = P (c z dP~ - delta), dV = P~^T dO.  Nothing is saved but o, lse and the ticket: every kernel recomputes z.
+// Stream: element (b, h, i, j) has mask index m = 4 (((b H + h) ceil(T / 4) + (i >> 2)) S + j) + (i & 3) -- the linear
+// index into a contiguous [B H, ceil(T / 4), S, 4] array -- and from there on it is the stream of dropout.h (group
+// m >> 2, word m & 3, dropped iff word < thr), so the mask is independent of the tiling.  Four rows of one key share a
+// Philox block: in k_attn_fwd and k_attn_dq a lane's accumulator holds rows r0 .. r0 + 3 (r0 a multiple of 4) of key
+// k0 + 16 t + c, i.e. the four words of one block per t, four calls per lane and 64-key tile, issued ahead of the
+// S = Q K^T MFMAs they do not depend on.  In k_attn_dkv the accumulator is transposed (keys j0 .. j0 + 3 of query
+// q0 + 16 t + c): the four lanes of a quad share a row group, the lane at quad position n computes the block of key
+// j0 + n, and the quad transposes the 4 x 4 words by two DPP quad_perm exchanges (xor 1, xor 2) with selects -- four
+// calls per lane and tile again.  The forward takes and advances the ticket by the protocol of dropout.h over the
+// linear workgroup id of its three-dimensional grid; the backward kernels read it from ticket_in.  No LDS is added.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -51,6 +66,13 @@ struct AttnArgs {
   int B, H, T, S, D, Dv;
   int causal;
   float scale;
+  // attention dropout: on iff state or ticket_in is set (dropout.h: the stream and the ticket protocol)
+  int64_t* state;            // forward: [calls, arrivals]; backward: null
+  const int64_t* ticket_in;  // backward: the forward's ticket; forward: null
+  int64_t* ticket_out;       // forward: receives the ticket used; backward: null
+  uint32_t k0, k1;
+  uint64_t thr;  // <= 2^32
+  float keep;    // 1 / (1 - rate)
 };
 
 struct AttnPlan {

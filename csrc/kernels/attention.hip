@@ -4,6 +4,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "philox_ticket.h"
 
 namespace tdl {
 namespace {
@@ -108,8 +109,56 @@ __device__ __forceinline__ bool admitted(const AttnArgs& a, int b, int h, int ro
   return ok;
 }
 
+// ---- attention dropout (attention.h): the constants of a launch, the words of a group, the keep rule ----
+struct Drop {
+  uint32_t k0, k1, t_lo, t_hi, thr_lo;
+  bool all;  // thr == 2^32
+  float c;
+  __device__ __forceinline__ void block(uint64_t g, uint32_t (&o)[4]) const {
+    philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), t_lo, t_hi, k0, k1, o);
+  }
+  __device__ __forceinline__ bool keep(uint32_t w) const { return !all && w >= thr_lo; }
+};
+__device__ __forceinline__ unsigned wg_linear() { return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z); }
+__device__ __forceinline__ unsigned wg_count() { return gridDim.x * gridDim.y * gridDim.z; }
+__device__ __forceinline__ Drop make_drop(const AttnArgs& a, unsigned long long t) {
+  Drop r;
+  r.k0 = a.k0, r.k1 = a.k1;
+  r.t_lo = (uint32_t)t, r.t_hi = (uint32_t)(t >> 32);
+  r.thr_lo = (uint32_t)a.thr, r.all = (a.thr >> 32) != 0;
+  r.c = a.keep;
+  return r;
+}
+// group of mask elements (rows 4 rg .. 4 rg + 3, key 0) of (b, h); the key is added to it
+__device__ __forceinline__ uint64_t drop_group(const AttnArgs& a, int b, int h, int rg) {
+  return (((uint64_t)b * a.H + h) * (uint64_t)((a.T + 3) >> 2) + (uint64_t)rg) * (uint64_t)a.S;
+}
+__device__ __forceinline__ uint32_t quad_xor1(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);
+}
+__device__ __forceinline__ uint32_t quad_xor2(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false);
+}
+// the lane at position n of a quad enters with row n of a 4 x 4 matrix and leaves with column n (o[i] = word n of
+// lane i's row): 2 x 2 blocks exchanged within the pairs (xor 1), then between them (xor 2)
+__device__ __forceinline__ void quad_transpose(uint32_t (&o)[4], int n) {
+  const bool b0 = (n & 1) != 0, b1 = (n & 2) != 0;
+#pragma unroll
+  for (int p = 0; p < 4; p += 2) {
+    const uint32_t r = quad_xor1(b0 ? o[p] : o[p + 1]);
+    o[p] = b0 ? r : o[p];
+    o[p + 1] = b0 ? o[p + 1] : r;
+  }
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const uint32_t r = quad_xor2(b1 ? o[p] : o[p + 2]);
+    o[p] = b1 ? r : o[p];
+    o[p + 2] = b1 ? o[p + 2] : r;
+  }
+}
+
 // ---- forward ----
-template <bool BF, int HD>
+template <bool BF, int HD, bool DROP>
 __global__ __launch_bounds__(kThreads) void k_attn_fwd(const AttnArgs a) {
   using T = typename Lay<BF, HD>::T;
   using Frag = typename Lay<BF, HD>::Frag;
@@ -141,6 +190,14 @@ __global__ __launch_bounds__(kThreads) void k_attn_fwd(const AttnArgs a) {
   for (int i = 0; i < 4; ++i) m[i] = -INFINITY, ls[i] = 0.f;
   const int r0 = q0 + 16 * w + 4 * g;  // this lane's accumulator rows r0 + i
   T* strip = sP + w * 16 * M::ST;
+  Drop R;
+  uint64_t gq = 0;  // the group of (rows r0 .. r0 + 3, key c)
+  unsigned long long ticket = 0;
+  if constexpr (DROP) {
+    ticket = ticket_read(a.state, a.ticket_in, a.ticket_out, wg_linear());
+    R = make_drop(a, ticket);
+    gq = drop_group(a, b, h, r0 >> 2) + c;
+  }
 
   const int kts = (a.S + kAttnTile - 1) / kAttnTile;
   const int nkt = a.causal ? min(kts, qt + 1) : kts;
@@ -150,6 +207,18 @@ __global__ __launch_bounds__(kThreads) void k_attn_fwd(const AttnArgs a) {
     stage<BF, HD, true, false>(sK, nullptr, k, a.ks[1], k0, a.S, a.D);
     stage<BF, HD, false, true>(nullptr, sVt, v, a.vs[1], k0, a.S, a.Dv);
     __syncthreads();
+    // the tile's keep bits (bit 4 t + i: row r0 + i, key k0 + 16 t + c), from indices alone: ahead of the MFMA
+    // chain, so that the scheduler runs the Philox rounds under it
+    uint32_t zm = 0;
+    if constexpr (DROP) {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        uint32_t o[4];
+        R.block(gq + (uint64_t)(k0 + 16 * t), o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) zm |= (uint32_t)R.keep(o[i]) << (4 * t + i);
+      }
+    }
     f4 s[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -173,8 +242,9 @@ __global__ __launch_bounds__(kThreads) void k_attn_fwd(const AttnArgs a) {
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         const float p = __builtin_amdgcn_exp2f(s[t][i] - mu);
-        rs += p;
-        put(strip + (4 * g + i) * M::ST + 16 * t + c, p);
+        rs += p;  // (the undropped row's sum)
+        if constexpr (DROP) put(strip + (4 * g + i) * M::ST + 16 * t + c, (zm >> (4 * t + i)) & 1u ? p * R.c : 0.f);
+        else put(strip + (4 * g + i) * M::ST + 16 * t + c, p);
       }
       ls[i] = ls[i] * al + row_sum(rs);
       m[i] = mn;
@@ -204,6 +274,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_fwd(const AttnArgs a) {
     if (c == 0)
       a.lse[((int64_t)b * a.H + h) * a.T + row] = ls[i] > 0.f ? (m[i] + __builtin_amdgcn_logf(ls[i])) * kLn2 : -INFINITY;
   }
+  if constexpr (DROP) ticket_arrive(a.state, ticket, wg_count());
 }
 
 // ---- delta = rowsum(do * o) ----
@@ -223,7 +294,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_delta(const AttnArgs a) {
 }
 
 // ---- dQ ----
-template <bool BF, int HD>
+template <bool BF, int HD, bool DROP>
 __global__ __launch_bounds__(kThreads) void k_attn_dq(const AttnArgs a) {
   using T = typename Lay<BF, HD>::T;
   using Frag = typename Lay<BF, HD>::Frag;
@@ -263,6 +334,12 @@ __global__ __launch_bounds__(kThreads) void k_attn_dq(const AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < M::NTH; ++t) dQ[t] = zero4();
   T* strip = sP + w * 16 * M::ST;
+  Drop R;
+  uint64_t gq = 0;  // the group of (rows r0 .. r0 + 3, key c)
+  if constexpr (DROP) {
+    R = make_drop(a, ticket_read(nullptr, a.ticket_in, nullptr, 0u));
+    gq = drop_group(a, b, h, r0 >> 2) + c;
+  }
 
   const int kts = (a.S + kAttnTile - 1) / kAttnTile;
   const int nkt = a.causal ? min(kts, qt + 1) : kts;
@@ -274,6 +351,8 @@ __global__ __launch_bounds__(kThreads) void k_attn_dq(const AttnArgs a) {
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
+      uint32_t z[4];  // the words of rows r0 + i, key k0 + 16 t + c (indices alone: ahead of the MFMAs)
+      if constexpr (DROP) R.block(gq + (uint64_t)(k0 + 16 * t), z);
       f4 s = zero4(), dp = zero4();
 #pragma unroll
       for (int ch = 0; ch < M::NCH; ++ch) {
@@ -283,7 +362,8 @@ __global__ __launch_bounds__(kThreads) void k_attn_dq(const AttnArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float p = admitted(a, b, h, r0 + i, k0 + 16 * t + c) ? __builtin_amdgcn_exp2f(s[i] * cs - l2[i]) : 0.f;
-        put(strip + (4 * g + i) * M::ST + 16 * t + c, p * (dp[i] - dl[i]));
+        if constexpr (DROP) put(strip + (4 * g + i) * M::ST + 16 * t + c, p * ((R.keep(z[i]) ? R.c * dp[i] : 0.f) - dl[i]));
+        else put(strip + (4 * g + i) * M::ST + 16 * t + c, p * (dp[i] - dl[i]));
       }
     }
     __syncthreads();
@@ -307,7 +387,7 @@ __global__ __launch_bounds__(kThreads) void k_attn_dq(const AttnArgs a) {
 }
 
 // ---- dK, dV ----
-template <bool BF, int HD>
+template <bool BF, int HD, bool DROP>
 __global__ __launch_bounds__(kThreads) void k_attn_dkv(const AttnArgs a) {
   using T = typename Lay<BF, HD>::T;
   using Frag = typename Lay<BF, HD>::Frag;
@@ -341,6 +421,12 @@ __global__ __launch_bounds__(kThreads) void k_attn_dkv(const AttnArgs a) {
 #pragma unroll
   for (int t = 0; t < M::NTH; ++t) dK[t] = zero4(), dV[t] = zero4();
   T* strip = sP + w * 16 * M::ST;
+  Drop R;
+  uint64_t gk = 0;  // the group of (row group 0, key j0 + n), n = c & 3: this lane's share of its quad's four blocks
+  if constexpr (DROP) {
+    R = make_drop(a, ticket_read(nullptr, a.ticket_in, nullptr, 0u));
+    gk = drop_group(a, b, h, 0) + (uint64_t)(j0 + (c & 3));
+  }
 
   const int qts = (a.T + kAttnTile - 1) / kAttnTile;
   for (int qt = a.causal ? kt : 0; qt < qts; ++qt) {
@@ -359,6 +445,13 @@ __global__ __launch_bounds__(kThreads) void k_attn_dkv(const AttnArgs a) {
     f4 ds[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
+      // z[i]: the word of (query q0 + 16 t + c, key j0 + i).  The query is row c & 3 of its group of four, which
+      // the lanes of a quad share: each computes the block of one of the four keys, the quad transposes the words
+      uint32_t z[4];
+      if constexpr (DROP) {
+        R.block(gk + (uint64_t)((q0 + 16 * t + c) >> 2) * (uint64_t)a.S, z);
+        quad_transpose(z, c & 3);
+      }
       f4 s = zero4(), dp = zero4();
 #pragma unroll
       for (int ch = 0; ch < M::NCH; ++ch) {
@@ -369,8 +462,14 @@ __global__ __launch_bounds__(kThreads) void k_attn_dkv(const AttnArgs a) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float p = admitted(a, b, h, q0 + 16 * t + c, j0 + i) ? __builtin_amdgcn_exp2f(s[i] * cs - l2) : 0.f;
-        put(strip + (4 * g + i) * M::ST + 16 * t + c, p);
-        ds[t][i] = p * (dp[i] - dl);
+        if constexpr (DROP) {
+          const bool kept = R.keep(z[i]);
+          put(strip + (4 * g + i) * M::ST + 16 * t + c, kept ? p * R.c : 0.f);
+          ds[t][i] = p * ((kept ? R.c * dp[i] : 0.f) - dl);
+        } else {
+          put(strip + (4 * g + i) * M::ST + 16 * t + c, p);
+          ds[t][i] = p * (dp[i] - dl);
+        }
       }
     }
     __syncthreads();
@@ -422,15 +521,22 @@ static_assert(lds_bytes<false, 128>(2) <= 160 * 1024, "LDS of a workgroup on gfx
 template <bool BF, int HD>
 void launch_fwd(const AttnArgs& a, hipStream_t s) {
   const dim3 grid((a.T + kAttnTile - 1) / kAttnTile, a.H, a.B);
-  hipLaunchKernelGGL((k_attn_fwd<BF, HD>), grid, dim3(kThreads), 0, s, a);
+  if (a.state != nullptr) hipLaunchKernelGGL((k_attn_fwd<BF, HD, true>), grid, dim3(kThreads), 0, s, a);
+  else hipLaunchKernelGGL((k_attn_fwd<BF, HD, false>), grid, dim3(kThreads), 0, s, a);
 }
 template <bool BF, int HD>
 void launch_bwd(const AttnArgs& a, hipStream_t s) {
   using T = typename Lay<BF, HD>::T;
   const int64_t rows = (int64_t)a.B * a.H * a.T;
   hipLaunchKernelGGL((k_attn_delta<T>), dim3((unsigned)((rows + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((k_attn_dq<BF, HD>), dim3((a.T + kAttnTile - 1) / kAttnTile, a.H, a.B), dim3(kThreads), 0, s, a);
-  hipLaunchKernelGGL((k_attn_dkv<BF, HD>), dim3((a.S + kAttnTile - 1) / kAttnTile, a.H, a.B), dim3(kThreads), 0, s, a);
+  const dim3 gq((a.T + kAttnTile - 1) / kAttnTile, a.H, a.B), gk((a.S + kAttnTile - 1) / kAttnTile, a.H, a.B);
+  if (a.ticket_in != nullptr) {
+    hipLaunchKernelGGL((k_attn_dq<BF, HD, true>), gq, dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL((k_attn_dkv<BF, HD, true>), gk, dim3(kThreads), 0, s, a);
+  } else {
+    hipLaunchKernelGGL((k_attn_dq<BF, HD, false>), gq, dim3(kThreads), 0, s, a);
+    hipLaunchKernelGGL((k_attn_dkv<BF, HD, false>), gk, dim3(kThreads), 0, s, a);
+  }
 }
 
 }  // namespace

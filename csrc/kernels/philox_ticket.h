@@ -1,4 +1,4 @@
-// Device helpers shared by the seeded kernels (dropout.hip, augment.hip): the Philox4x32-10 block function
+// Device helpers shared by the seeded kernels (dropout.hip, augment.hip, attention.hip): the Philox4x32-10 block function
 // and the call-counter ("ticket") protocol.  The stream and the protocol are specified in dropout.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,30 +29,40 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 }
 
 // ---- ticket (dropout.h): state = [calls, arrivals], or null with the ticket in *ticket_in ----
+// wg / nwg: the workgroup's linear id and the workgroup count of the launch (grids of more than one dimension)
 __device__ __forceinline__ unsigned long long ticket_read(int64_t* state, const int64_t* ticket_in,
-                                                          int64_t* ticket_out) {
+                                                          int64_t* ticket_out, unsigned wg) {
   typedef unsigned long long u64;
   u64 t;
   if (state != nullptr)
     t = __hip_atomic_load(reinterpret_cast<u64*>(state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else
     t = (u64)*ticket_in;
-  if (ticket_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *ticket_out = (int64_t)t;
+  if (ticket_out != nullptr && wg == 0 && threadIdx.x == 0) *ticket_out = (int64_t)t;
   return t;
 }
 
-__device__ __forceinline__ void ticket_arrive(int64_t* state, unsigned long long t) {
+__device__ __forceinline__ void ticket_arrive(int64_t* state, unsigned long long t, unsigned nwg) {
   typedef unsigned long long u64;
   if (state == nullptr) return;
   __syncthreads();  // the workgroup's last store is issued
   if (threadIdx.x == 0) {
     u64* s = reinterpret_cast<u64*>(state);
     const u64 prev = __hip_atomic_fetch_add(s + 1, (u64)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (prev == (u64)gridDim.x - 1) {  // every workgroup has read calls: advance it for the next launch
+    if (prev == (u64)nwg - 1) {  // every workgroup has read calls: advance it for the next launch
       __hip_atomic_store(s + 1, (u64)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(s, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+
+// one-dimensional grids
+__device__ __forceinline__ unsigned long long ticket_read(int64_t* state, const int64_t* ticket_in,
+                                                          int64_t* ticket_out) {
+  return ticket_read(state, ticket_in, ticket_out, blockIdx.x);
+}
+__device__ __forceinline__ void ticket_arrive(int64_t* state, unsigned long long t) {
+  ticket_arrive(state, t, gridDim.x);
 }
 
 }  // namespace tdl

@@ -1971,22 +1971,53 @@ tdl::AttnArgs attn_check(const at::Tensor& q, const at::Tensor& k, const at::Ten
   return a;
 }
 
-// (o [B,T,H,Dv] in q's dtype, lse f32 [B,H,T])
+// attention dropout (kernels/attention.h): rate 0 is none; otherwise 0 < rate < 1 and the Philox key; the threshold
+// and the keep scale are ops/dropout.py's threshold() and keep_scale()
+bool attn_dropout(tdl::AttnArgs& a, double rate, const c10::optional<std::pair<int64_t, int64_t>>& key, const char* what) {
+  if (rate == 0.0) return false;
+  TORCH_CHECK(rate > 0.0 && rate < 1.0, what, ": the dropout rate must be in [0, 1), got ", rate);
+  TORCH_CHECK(key.has_value() && key->first >= 0 && key->first <= 0xffffffffLL && key->second >= 0 &&
+                  key->second <= 0xffffffffLL, what, ": dropout needs a key of two 32-bit words");
+  a.k0 = (uint32_t)key->first, a.k1 = (uint32_t)key->second;
+  a.thr = (uint64_t)(rate * 4294967296.0);
+  a.keep = (float)(1.0 / (1.0 - rate));
+  return true;
+}
+
+// (o [B,T,H,Dv] in q's dtype, lse f32 [B,H,T]); with rate > 0 also the int64 [1] ticket the mask was drawn with
 std::vector<at::Tensor> attn_forward(at::Tensor q, at::Tensor k, at::Tensor v, double scale, bool causal,
-                                     c10::optional<at::Tensor> mask) {
+                                     c10::optional<at::Tensor> mask, double rate,
+                                     c10::optional<std::pair<int64_t, int64_t>> key, c10::optional<at::Tensor> state) {
   tdl::AttnArgs a = attn_check(q, k, v, scale, causal, mask, "attention");
   auto o = fresh({a.B, a.T, a.H, a.Dv}, q.options());
   auto lse = fresh({a.B, a.H, a.T}, q.options().dtype(at::kFloat));
   a.o = o.data_ptr(), a.lse = lse.data_ptr<float>();
+  at::Tensor ticket;
+  const bool drop = attn_dropout(a, rate, key, "attention");
+  if (drop) {
+    TORCH_CHECK(state.has_value() && state->is_cuda() && state->scalar_type() == at::kLong && state->numel() == 2 &&
+                    state->is_contiguous() && state->device() == q.device(),
+                "attention: dropout needs state, an int64 [calls, arrivals] tensor on q's device");
+    ticket = at::empty({1}, state->options());
+    a.state = state->data_ptr<int64_t>(), a.ticket_out = ticket.data_ptr<int64_t>();
+  }
   tdl::attn_forward(a, q.scalar_type() == at::kBFloat16, cur_stream());
+  if (drop) return {o, lse, ticket};
   return {o, lse};
 }
 
 // (dq, dk, dv), contiguous, in q's dtype
 std::vector<at::Tensor> attn_backward(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
-                                      at::Tensor dout, double scale, bool causal, c10::optional<at::Tensor> mask) {
+                                      at::Tensor dout, double scale, bool causal, c10::optional<at::Tensor> mask,
+                                      double rate, c10::optional<std::pair<int64_t, int64_t>> key,
+                                      c10::optional<at::Tensor> ticket) {
   const char* what = "attention backward";
   tdl::AttnArgs a = attn_check(q, k, v, scale, causal, mask, what);
+  if (attn_dropout(a, rate, key, what)) {
+    TORCH_CHECK(ticket.has_value() && ticket->is_cuda() && ticket->scalar_type() == at::kLong && ticket->numel() == 1 &&
+                    ticket->device() == q.device(), what, ": dropout needs the forward's 1-element int64 ticket");
+    a.ticket_in = ticket->data_ptr<int64_t>();
+  }
   attn_operand(dout, q, a.gs, what, "do");
   TORCH_CHECK(o.is_cuda() && o.is_contiguous() && o.scalar_type() == q.scalar_type() &&
                   o.sizes() == at::IntArrayRef({a.B, a.T, a.H, a.Dv}) && dout.sizes() == o.sizes(), what,
@@ -2024,12 +2055,18 @@ pybind11::dict attn_plan(int64_t B, int64_t H, int64_t T, int64_t S, int64_t D, 
 }  // namespace
 
 void register_ops(pybind11::module& m) {
-  m.def("attn_forward", &attn_forward, "fused scaled-dot-product attention forward over strided [B,T,H,D] views: (o, lse)",
+  m.def("attn_forward", &attn_forward,
+        "fused scaled-dot-product attention forward over strided [B,T,H,D] views: (o, lse); with rate > 0 (seeded "
+        "dropout on the probabilities: key = (k0, k1), state = the int64 [calls, arrivals] tensor): (o, lse, ticket)",
         pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("scale"), pybind11::arg("causal"),
-        pybind11::arg("mask") = pybind11::none());
-  m.def("attn_backward", &attn_backward, "fused attention backward (delta, dQ, dK/dV kernels; no atomics): (dq, dk, dv)",
+        pybind11::arg("mask") = pybind11::none(), pybind11::arg("rate") = 0.0, pybind11::arg("key") = pybind11::none(),
+        pybind11::arg("state") = pybind11::none());
+  m.def("attn_backward", &attn_backward,
+        "fused attention backward (delta, dQ, dK/dV kernels; no atomics): (dq, dk, dv); rate, key and the forward's "
+        "ticket recompute a dropout forward's mask",
         pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
-        pybind11::arg("do"), pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("mask") = pybind11::none());
+        pybind11::arg("do"), pybind11::arg("scale"), pybind11::arg("causal"), pybind11::arg("mask") = pybind11::none(),
+        pybind11::arg("rate") = 0.0, pybind11::arg("key") = pybind11::none(), pybind11::arg("ticket") = pybind11::none());
   m.def("attn_plan", &attn_plan, "fused attention plan as a dict (raises outside the kernels' limits); no GPU needed",
         pybind11::arg("B"), pybind11::arg("H"), pybind11::arg("T"), pybind11::arg("S"), pybind11::arg("D"),
         pybind11::arg("Dv"), pybind11::arg("bf16"), pybind11::arg("causal"));

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times the fused attention kernels (ops/attention.py) against F.scaled_dot_product_attention and the unfused torch
-formula: forward and forward + backward, f32 and bf16.  Device time from HIP events around a window of back-to-back
+formula: forward and forward + backward, f32 and bf16, and with attention dropout (rate 0.1): inside the kernels
+against the formula with F.dropout.  Device time from HIP events around a window of back-to-back
 calls sized to `--window` seconds from a first estimate (a short window measures the scheduler); the three paths are
 timed in turn within each of `--reps` rounds, so drift hits them alike.  Prints one JSON line per (shape, dtype,
 path): the median and the [min, max] of the rounds, ms per call.
@@ -20,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tensorflow_distributed_learning_amd.ops import attention as A  # noqa: E402
 
 SHAPES = [(64, 8, 128, 128, 64, False), (8, 12, 512, 512, 64, False), (4, 16, 2048, 2048, 128, True)]
+RATE, KEY = 0.1, (0x243F6A88, 0x85A308D3)
 
 
 def _window(fn, iters):
@@ -49,7 +51,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=0.3)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--only", default="", help="comma-separated paths to time (default: all)")
     args = ap.parse_args()
+    state = torch.zeros(2, dtype=torch.int64, device="cuda")  # the dropout call counter [calls, arrivals]
     for B, H, T, S, D, causal in SHAPES:
         for dtype in (torch.float32, torch.bfloat16):
             g = torch.Generator(device="cuda").manual_seed(0)
@@ -60,7 +64,12 @@ def main():
                 "library": lambda: F.scaled_dot_product_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
                                                                   is_causal=causal).transpose(1, 2),
                 "formula": lambda: A.sdpa_torch(q, k, v, None, causal),
+                # attention dropout at RATE: inside the kernels (seeded Philox), and the formula with F.dropout
+                "kernels_dropout": lambda: A.sdpa(q, k, v, None, causal, rate=RATE, key=KEY, state=state),
+                "formula_dropout": lambda: A.sdpa_torch(q, k, v, None, causal, dropout=lambda p: F.dropout(p, RATE, True)),
             }
+            if args.only:
+                paths = {n: f for n, f in paths.items() if n in args.only.split(",")}
 
             def both(fn):
                 def run():

@@ -1552,7 +1552,7 @@ class Embedding(Layer):
         return tuple(s) + (self.output_dim,)
 
 
-class MultiHeadAttention(Layer):
+class MultiHeadAttention(_CallCounterRNG, Layer):
     """tf.keras.layers.MultiHeadAttention over rank-3 inputs: ``layer(query [B,T,dim], value [B,S,dim'], key=None,
     attention_mask=None [B,T,S], use_causal_mask=False, return_attention_scores=False)``.  Weights, with Keras' names
     and shapes: ``query/kernel [dim,H,D]``, ``query/bias [H,D]``, the same for ``key``, ``value/kernel [dim',H,Dv]``,
@@ -1561,17 +1561,29 @@ class MultiHeadAttention(Layer):
     The four projections run through Dense's dispatch (the f32 / bf16 MFMA GEMMs on the GPU, gradients straight into
     the trainer's slab); their outputs reach the fused attention kernels (ops/attention.py) as ``[B,T,H,D]`` views,
     without a permute.  A query row whose mask admits no key gives the output bias alone (Keras: the projected mean
-    of the values).  Attention dropout in training and ``return_attention_scores`` use the torch formula."""
+    of the values).
+
+    Attention dropout (``dropout > 0`` in training) runs inside the same kernels: the probabilities are dropped by
+    the reproducible Philox stream of ``Dropout`` (ops/dropout.py) -- a function of (``seed``, the layer's stream, the
+    replica, the call number), the same mask on the CPU, on the torch-formula path and in replayed graphs, recomputed
+    in the backward.  ``seed`` follows ``Dropout``'s rules: an explicit seed uses stream 0, ``None`` the global seed and
+    the layer's creation index -- taken only when ``dropout > 0``, so a layer without dropout moves no other layer's
+    stream.  ``return_attention_scores`` uses the torch formula and returns the undropped probabilities."""
 
     def __init__(self, num_heads, key_dim, value_dim=None, dropout=0.0, use_bias=True, output_shape=None,
                  attention_axes=None, kernel_initializer="glorot_uniform", bias_initializer="zeros",
-                 kernel_regularizer=None, bias_regularizer=None, **kw):
+                 kernel_regularizer=None, bias_regularizer=None, seed=None, **kw):
         super().__init__(**kw)
         if attention_axes is not None:
             raise ValueError("MultiHeadAttention: attention_axes other than None is not implemented")
         self.num_heads, self.key_dim = int(num_heads), int(key_dim)
         self.value_dim = int(value_dim) if value_dim is not None else self.key_dim
         self.dropout, self.use_bias = float(dropout), bool(use_bias)
+        if not 0.0 <= self.dropout < 1.0:
+            raise ValueError(f"MultiHeadAttention: dropout must be in [0, 1), got {dropout!r}")
+        # (a layer that never draws takes no creation-order stream index: an explicit seed takes none)
+        self._init_rng(seed if self.dropout > 0 or seed is not None else 0)
+        self.seed = None if seed is None else int(seed)
         if output_shape is not None and not isinstance(output_shape, int):
             if len(output_shape) != 1:
                 raise ValueError("MultiHeadAttention: output_shape must be None, an int or a 1-tuple")
@@ -1630,14 +1642,18 @@ class MultiHeadAttention(Layer):
         if mask is not None:
             mask = (mask if mask.dtype == torch.bool else mask != 0).expand(B, T, S)
         scores = None
-        if return_attention_scores or (training and self.dropout > 0):
-            drop = (lambda p: F.dropout(p, self.dropout, True)) if training and self.dropout > 0 else None
-            o = _attn.sdpa_torch(q, k, v, None, use_causal_mask, mask, dropout=drop,
-                                 return_scores=return_attention_scores)
-            if return_attention_scores:
-                o, scores = o
+        rng = {}
+        if training and self.dropout > 0:  # one ticket per call, on every path
+            rng = dict(rate=self.dropout, key=self._key())
+            if q.is_cuda:
+                rng["state"] = self._state_for(q.device)
+            else:
+                rng["ticket"] = self._take_cpu_ticket()
+        if return_attention_scores:
+            o, scores = _attn.sdpa_torch(q, k, v, None, use_causal_mask, mask, return_scores=True,
+                                         dropout=_attn.philox_dropout(**rng) if rng else None)
         else:
-            o = _attn.sdpa(q, k, v, None, use_causal_mask, mask)
+            o = _attn.sdpa(q, k, v, None, use_causal_mask, mask, **rng)
         w, b = self.o_proj
         y = _dense_rows(o.reshape(B, T, H * Dv), w, b, w.shape[2], ident, (H * Dv, w.shape[2]))
         return (y, scores) if return_attention_scores else y
@@ -1650,7 +1666,7 @@ class MultiHeadAttention(Layer):
         cfg = dict(super().get_config(), num_heads=self.num_heads, key_dim=self.key_dim, value_dim=self.value_dim,
                    dropout=self.dropout, use_bias=self.use_bias, output_shape=self.output_dim,
                    kernel_initializer=_init.serialize(self.kernel_initializer),
-                   bias_initializer=_init.serialize(self.bias_initializer))
+                   bias_initializer=_init.serialize(self.bias_initializer), seed=self.seed)
         for k in ("kernel_regularizer", "bias_regularizer"):  # (only when set, as the other layers' configs)
             if getattr(self, k) is not None:
                 cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))

@@ -1,6 +1,6 @@
 """Scaled-dot-product attention on the fused MFMA kernels of csrc/kernels/attention.hip.
 
-``sdpa(q, k, v, scale=None, causal=False, mask=None)``: ``q [B,T,H,D]``, ``k [B,S,H,D]``, ``v [B,S,H,Dv]`` (f32 or
+``sdpa(q, k, v, scale=None, causal=False, mask=None, rate=0.0, key=None, state=None, ticket=None)``: ``q [B,T,H,D]``, ``k [B,S,H,D]``, ``v [B,S,H,Dv]`` (f32 or
 bf16, any strides on the first three axes: projection outputs and slices of a packed qkv buffer are consumed as
 views, no permute or copy is launched) give ``o [B,T,H,Dv]``::
 
@@ -12,7 +12,9 @@ an admitted key gives ``o = 0`` and zero gradients, never NaN -- Keras gives the
 
 Kernels (csrc/kernels/attention.h): a flash-style forward that never writes the ``[B,H,T,S]`` matrix and saves only
 ``o`` and the f32 row normaliser ``lse``; the backward is three launches (delta, dQ by query tile, dK/dV by key
-tile) that recompute the probabilities -- no atomics, the same bits on every run.
+tile) that recompute the probabilities -- no atomics, the same bits on every run.  With ``rate > 0`` the tile kernels
+drop probabilities by the seeded Philox stream of ops/dropout.py (``o = (c z P) V``, ``lse`` of the undropped row; the
+mask is recomputed in the backward from the saved ticket), and :func:`philox_dropout` draws the same mask for the formula.
 
 :func:`supported` mirrors the binding's checks (:func:`limits_ok` is their device-independent part): GPU tensors of
 one dtype, f32 or bf16; ``D, Dv <= 128`` and multiples of 8; a contiguous, 16-byte aligned innermost axis with strides that are multiples of 16 bytes; every
@@ -80,25 +82,35 @@ def _u8(mask):
 
 
 class _Attention(torch.autograd.Function):
+    """``rate > 0``: the forward kernel takes the ticket from ``state`` and advances it; the ticket tensor is saved
+    beside ``o`` and ``lse`` and the backward kernels recompute the mask from it."""
+
     @staticmethod
-    def forward(ctx, q, k, v, scale, causal, mask):
+    def forward(ctx, q, k, v, scale, causal, mask, rate=0.0, key=None, state=None):
         CALLS["forward"] += 1
-        o, lse = hip().attn_forward(q, k, v, scale, causal, mask)
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.args = (scale, causal, mask)
+        if rate > 0:
+            o, lse, ticket = hip().attn_forward(q, k, v, scale, causal, mask, rate, key, state)
+            ctx.save_for_backward(q, k, v, o, lse, ticket)
+        else:
+            o, lse = hip().attn_forward(q, k, v, scale, causal, mask)
+            ctx.save_for_backward(q, k, v, o, lse)
+        ctx.args = (scale, causal, mask, rate, key)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
-        scale, causal, mask = ctx.args
+        q, k, v, o, lse, *ticket = ctx.saved_tensors
+        scale, causal, mask, rate, key = ctx.args
         CALLS["backward"] += 1
         do = do.to(o.dtype)
         if not (_operand_ok(do) and do.data_ptr() % 16 == 0):
             do = do.contiguous()
             do = do if do.data_ptr() % 16 == 0 else do.clone()
-        dq, dk, dv = hip().attn_backward(q, k, v, o, lse, do, scale, causal, mask)
-        return dq, dk, dv, None, None, None
+        if rate > 0:
+            dq, dk, dv = hip().attn_backward(q, k, v, o, lse, do, scale, causal, mask, rate, key, ticket[0])
+        else:
+            dq, dk, dv = hip().attn_backward(q, k, v, o, lse, do, scale, causal, mask)
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 def admitted(T, S, causal, mask, device):
@@ -131,13 +143,43 @@ def sdpa_torch(q, k, v, scale=None, causal=False, mask=None, dropout=None, retur
     return (o, p.to(q.dtype)) if return_scores else o
 
 
-def sdpa(q, k, v, scale=None, causal=False, mask=None):
+def philox_dropout(rate, key, state=None, ticket=None):
+    """The kernels' attention dropout as ``sdpa_torch``'s ``dropout`` callable, on any device: ``p [B,H,T,S]`` is
+    padded to ``4 ceil(T / 4)`` rows and laid out as ``[B H, ceil(T / 4), S, 4]``, whose linear index is the kernels'
+    mask index (csrc/kernels/attention.h), and goes through :func:`ops.dropout.dropout` with a full-shape mask:
+    ``state`` on the GPU, ``ticket`` on the CPU, one ticket per call and the kernels' mask bit for bit."""
+    from . import dropout as _do
+
+    def apply(p):
+        B, H, T, S = p.shape
+        T4 = -(-T // 4)
+        x = torch.nn.functional.pad(p, (0, 0, 0, 4 * T4 - T)).reshape(B * H, T4, 4, S).permute(0, 1, 3, 2).contiguous()
+        y = _do.dropout(x, rate, key, state=state if p.is_cuda else None, ticket=None if p.is_cuda else ticket)
+        return y.permute(0, 1, 3, 2).reshape(B, H, 4 * T4, S)[:, :, :T]
+
+    return apply
+
+
+def sdpa(q, k, v, scale=None, causal=False, mask=None, rate=0.0, key=None, state=None, ticket=None):
+    """``rate > 0``: seeded dropout on the probabilities with the Philox ``key`` (``ops.dropout.stream_key``) and the
+    layer's call counter: the int64 ``state = [calls, arrivals]`` tensor of a GPU input's device, which the forward
+    kernel (or, on the formula path, the dropout kernel) advances, or the ``ticket`` number of a CPU input."""
     scale = 1.0 / math.sqrt(q.shape[3]) if scale is None else float(scale)
+    rate = float(rate)
+    if not 0.0 <= rate < 1.0:
+        raise ValueError(f"sdpa: the dropout rate must be in [0, 1), got {rate!r}")
+    drop = (0.0, None, None)
+    if rate > 0:
+        if key is None or (state is None if q.is_cuda else ticket is None):
+            raise ValueError("sdpa: dropout needs a key and the device state (GPU) or a ticket (CPU)")
+        key = (int(key[0]), int(key[1]))
+        drop = (rate, key, state)
     if q.is_cuda and not use_torch():
         if q.dtype in (torch.float16, torch.float64):
             f = [t.float() for t in (q, k, v)]  # converted once; the limits are those of the f32 copies
             if supported(*f, mask):
-                return _Attention.apply(*f, scale, bool(causal), _u8(mask)).to(q.dtype)
+                return _Attention.apply(*f, scale, bool(causal), _u8(mask), *drop).to(q.dtype)
         if supported(q, k, v, mask):
-            return _Attention.apply(q, k, v, scale, bool(causal), _u8(mask))
-    return sdpa_torch(q, k, v, scale, causal, mask)
+            return _Attention.apply(q, k, v, scale, bool(causal), _u8(mask), *drop)
+    return sdpa_torch(q, k, v, scale, causal, mask,
+                      dropout=philox_dropout(rate, key, state, ticket) if rate > 0 else None)
