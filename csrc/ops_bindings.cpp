@@ -15,6 +15,7 @@
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/groupnorm.h"
+#include "kernels/layernorm.h"
 #include "kernels/depthwise.h"
 #include "kernels/grouped_conv.h"
 #include "kernels/conv_transpose.h"
@@ -1561,6 +1562,106 @@ std::vector<at::Tensor> gn_backward(at::Tensor dy, at::Tensor x, int64_t G, c10:
   return {dx, pg ? *dgamma_out : out[0], pb ? *dbeta_out : out[1], part, coef};
 }
 
+// ---- layer / RMS normalisation (kernels/layernorm.h) over the last dimension of a contiguous [R, C] tensor
+struct LnShape {
+  int64_t R, C;
+  tdl::LnDType dt;
+  tdl::LnPlan plan;
+};
+LnShape ln_check(const at::Tensor& x, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 2, what, ": contiguous [R, C] GPU tensor expected");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, what, ": float32 or bfloat16 expected");
+  TORCH_CHECK(x.numel() > 0, what, ": empty tensor");
+  LnShape sh;
+  sh.R = x.size(0);
+  sh.C = x.size(1);
+  sh.dt = x.scalar_type() == at::kFloat ? tdl::LnDType::kF32 : tdl::LnDType::kBF16;
+  TORCH_CHECK(sh.C <= tdl::kLnMaxC, what, ": C <= ", tdl::kLnMaxC, " expected");
+  sh.plan = tdl::ln_plan(sh.R, (int)sh.C, sh.dt);
+  TORCH_CHECK(sh.plan.vec > 1 || sh.C <= tdl::kLnMaxCPerElement, what, ": a row of more than ",
+              tdl::kLnMaxCPerElement, " elements must be a multiple of 16 bytes");
+  TORCH_CHECK(sh.plan.vec == 1 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, what,
+              ": 16-byte aligned data expected");
+  // a grid of 2^32 threads and more does not launch
+  TORCH_CHECK(sh.plan.fwd_blocks < (int64_t(1) << 24), what, ": 2^24 workgroups or more");
+  return sh;
+}
+const float* ln_param(const c10::optional<at::Tensor>& t, const LnShape& sh, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kFloat && t->is_contiguous() && t->numel() == sh.C, what,
+              ": f32 [C] GPU parameters expected");
+  TORCH_CHECK(sh.plan.vec == 1 || reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, what,
+              ": 16-byte aligned parameters expected");
+  return t->data_ptr<float>();
+}
+
+// (y, stats f64 [R][2] = mean, 1/sqrt(var + eps))
+std::vector<at::Tensor> ln_forward(at::Tensor x, c10::optional<at::Tensor> gamma, c10::optional<at::Tensor> beta,
+                                   double eps, bool rms) {
+  const LnShape sh = ln_check(x, "layer_norm");
+  auto y = fresh(x.sizes(), x.options());
+  auto stats = fresh({sh.R, 2}, x.options().dtype(at::kDouble));
+  tdl::ln_forward(x.data_ptr(), y.data_ptr(), sh.dt, sh.R, (int)sh.C, ln_param(gamma, sh, "layer_norm"),
+                  ln_param(beta, sh, "layer_norm"), eps, rms, stats.data_ptr<double>(), cur_stream());
+  return {y, stats};
+}
+
+// (dx, dgamma, dbeta).  dgamma_out / dbeta_out: f32 [C] tensors the parameter gradients are ADDED into (a
+// trainer's slab views); the returned dgamma / dbeta are then those tensors.  want_params = false: dx alone
+// (dgamma / dbeta come back undefined); rms: no dbeta
+std::vector<at::Tensor> ln_backward(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> gamma, at::Tensor stats,
+                                    bool rms, c10::optional<at::Tensor> dgamma_out,
+                                    c10::optional<at::Tensor> dbeta_out, bool want_params) {
+  const LnShape sh = ln_check(x, "layer_norm backward");
+  ln_check(dy, "layer_norm backward");
+  TORCH_CHECK(dy.scalar_type() == x.scalar_type() && dy.sizes() == x.sizes(), "layer_norm backward: dy/x mismatch");
+  TORCH_CHECK(stats.is_cuda() && stats.is_contiguous() && stats.scalar_type() == at::kDouble &&
+                  stats.numel() == sh.R * 2,
+              "layer_norm backward: stats must be f64 [R][2]");
+  auto f = x.options().dtype(at::kFloat);
+  auto dx = fresh(x.sizes(), x.options());
+  auto check_out = [&](const c10::optional<at::Tensor>& t) {
+    if (!t.has_value() || !t->defined()) return (float*)nullptr;
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == at::kFloat && t->numel() == sh.C,
+                "layer_norm backward: gradient outputs must be contiguous f32 [C]");
+    return t->data_ptr<float>();
+  };
+  float* pg = check_out(dgamma_out);
+  float* pb = rms ? nullptr : check_out(dbeta_out);
+  const float* g = ln_param(gamma, sh, "layer_norm backward");
+  if (!want_params && !pg && !pb) {
+    tdl::ln_backward(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), sh.dt, sh.R, (int)sh.C, g, stats.data_ptr<double>(),
+                     rms, nullptr, nullptr, nullptr, 0, cur_stream());
+    return {dx, at::Tensor(), at::Tensor()};
+  }
+  auto part = fresh({sh.plan.blocks, 2, sh.C}, x.options().dtype(at::kDouble));
+  auto out = fresh({2, sh.C}, f);
+  float* o = out.data_ptr<float>();
+  const int acc = (pg ? 1 : 0) | (pb ? 2 : 0);
+  tdl::ln_backward(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), sh.dt, sh.R, (int)sh.C, g, stats.data_ptr<double>(), rms,
+                   part.data_ptr<double>(), pg ? pg : o, rms ? nullptr : (pb ? pb : o + sh.C), acc, cur_stream());
+  return {dx, pg ? *dgamma_out : out[0], rms ? at::Tensor() : (pb ? *dbeta_out : out[1])};
+}
+
+pybind11::dict ln_plan(int64_t R, int64_t C, bool bf16) {
+  TORCH_CHECK(R >= 1 && C >= 1 && C <= tdl::kLnMaxC, "ln_plan: R >= 1 and 1 <= C <= ", tdl::kLnMaxC, " expected");
+  const tdl::LnPlan p = tdl::ln_plan(R, (int)C, bf16 ? tdl::LnDType::kBF16 : tdl::LnDType::kF32);
+  pybind11::dict d;
+  d["vec"] = p.vec;
+  d["plan"] = p.plan;
+  d["L"] = p.L;
+  d["rows_fwd"] = p.rpi;
+  d["L_bwd"] = p.Lb;
+  d["rows_wg"] = p.rows_wg;
+  d["blocks"] = p.blocks;
+  d["sub_wave_max_c"] = tdl::kLnSubWaveMaxC;
+  d["sub_max_c"] = tdl::kLnSubMaxC;
+  d["wave_max_c"] = tdl::kLnWaveMaxC;
+  d["max_c"] = tdl::kLnMaxC;
+  d["max_c_per_element"] = tdl::kLnMaxCPerElement;
+  return d;
+}
+
 // ---- depthwise convolution (kernels/depthwise.h): x [N,H,W,C], w f32 [kh,kw,C,dm], y [N,OH,OW,C*dm]
 // geo = (sh, sw, dh, dw, pt, pl)
 struct DwShape {
@@ -2082,6 +2183,15 @@ void register_ops(pybind11::module& m) {
     const tdl::GnPlan p = tdl::gn_plan(P, (int)C, bf16 ? tdl::GnDType::kBF16 : tdl::GnDType::kF32);
     return std::vector<int64_t>{p.vec, p.cols, p.tc, p.rl, p.colblocks, p.rows_wg, p.chunks};
   }, "group normalisation plan for (P, C, dtype): vec, cols, tc, rl, colblocks, rows_wg, chunks");
+  m.def("ln_forward", &ln_forward, "layer / RMS normalisation over the last dimension of [R, C]: (y, stats)",
+        pybind11::arg("x"), pybind11::arg("gamma"), pybind11::arg("beta"), pybind11::arg("eps"),
+        pybind11::arg("rms") = false);
+  m.def("ln_backward", &ln_backward, "layer / RMS normalisation backward: (dx, dgamma, dbeta)",
+        pybind11::arg("dy"), pybind11::arg("x"), pybind11::arg("gamma"), pybind11::arg("stats"),
+        pybind11::arg("rms") = false, pybind11::arg("dgamma_out") = pybind11::none(),
+        pybind11::arg("dbeta_out") = pybind11::none(), pybind11::arg("want_params") = true);
+  m.def("ln_plan", &ln_plan, "layer normalisation plan for (R, C, dtype) as a dict, with the plans' widths; no GPU needed",
+        pybind11::arg("R"), pybind11::arg("C"), pybind11::arg("bf16"));
   m.def("dw_forward", &dw_forward, "channels-last depthwise convolution forward (+ bias, + ReLU): y",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("geo"), pybind11::arg("out_h"),
         pybind11::arg("out_w"), pybind11::arg("act") = 0, pybind11::arg("out") = pybind11::none());

@@ -1517,22 +1517,78 @@ class GroupNormalization(Layer):
 
 
 class LayerNormalization(Layer):
-    def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, **kw):
+    """tf.keras.layers.LayerNormalization: each sample position is normalised over ``axis`` (one axis or a
+    list).  ``rms_scaling=True`` (Keras 3): ``y = x * rsqrt(mean(x^2) + epsilon) * gamma``, no centring and no
+    beta.  When the axes are the trailing ones, a GPU input runs on the hand-written row kernels
+    (ops/layernorm.py): f32 or bf16 data (``mixed_bfloat16``), gamma / beta in f32.  On the CPU the default
+    form is ``F.layer_norm``; any other axis uses the same formula in PyTorch ops."""
+
+    def __init__(self, axis=-1, epsilon=1e-3, center=True, scale=True, rms_scaling=False, beta_initializer="zeros",
+                 gamma_initializer="ones", beta_regularizer=None, gamma_regularizer=None, **kw):
         super().__init__(**kw)
-        self.axis, self.epsilon, self.center, self.scale = axis, epsilon, center, scale
+        self.axis = list(axis) if isinstance(axis, (list, tuple)) else axis
+        self.epsilon, self.center, self.scale, self.rms_scaling = epsilon, center, scale, bool(rms_scaling)
+        self.beta_initializer = _init.get(beta_initializer)
+        self.gamma_initializer = _init.get(gamma_initializer)
+        self.beta_regularizer = GroupNormalization._regularizer(beta_regularizer)
+        self.gamma_regularizer = GroupNormalization._regularizer(gamma_regularizer)
+
+    def _axes(self, ndim):
+        axes = sorted({a % ndim for a in (self.axis if isinstance(self.axis, list) else [self.axis])})
+        if not axes or 0 in axes:
+            raise ValueError(f"{self.name}: axis {self.axis!r} of a rank-{ndim} input (axis 0 is the batch)")
+        return axes
 
     def build(self, input_shape):
-        c = int(input_shape[-1])
-        self.gamma = self.add_weight("gamma", (c,), initializer="ones") if self.scale else None
-        self.beta = self.add_weight("beta", (c,), initializer="zeros") if self.center else None
+        axes = self._axes(len(input_shape))
+        if any(input_shape[a] is None for a in axes):
+            raise ValueError(f"{self.name}: the axes {self.axis!r} of the input must have known sizes")
+        shape = tuple(int(input_shape[a]) for a in axes)
+        self.gamma = self.add_weight("gamma", shape, initializer=self.gamma_initializer,
+                                     regularizer=self.gamma_regularizer) if self.scale else None
+        self.beta = self.add_weight("beta", shape, initializer=self.beta_initializer,
+                                    regularizer=self.beta_regularizer) if self.center and not self.rms_scaling else None
         self.built = True
 
     def call(self, x, training=None):
-        return F.layer_norm(x, (x.shape[-1],), self.gamma.value if self.gamma else None,
-                            self.beta.value if self.beta else None, self.epsilon)
+        from ..ops import layernorm as _ln
+
+        axes = self._axes(x.dim())
+        k = len(axes)
+        trailing = axes == list(range(x.dim() - k, x.dim()))
+        gamma = self.gamma.value if self.gamma is not None else None
+        beta = self.beta.value if self.beta is not None else None
+        if not x.is_cuda and trailing and not self.rms_scaling:
+            return F.layer_norm(x, tuple(x.shape[-k:]), gamma, beta, self.epsilon)
+        if x.is_cuda:
+            x = _autocast_input(x)
+        if not trailing:
+            back = list(range(x.dim() - k, x.dim()))
+            y = _ln.layer_norm_torch(x.movedim(axes, back), gamma, beta, self.epsilon, self.rms_scaling, k)
+            return y.movedim(back, axes)
+        gt = self._grad_targets() if _ln.supported(x, k) and not _ln.use_torch() else None
+        return _ln.layer_norm(x, gamma, beta, self.epsilon, self.rms_scaling, grad_out=gt, axes=k)
+
+    def _grad_targets(self):
+        """(gamma, beta) slab views the backward kernel adds into directly, or None."""
+        if not self.trainable:
+            return None
+        t = tuple(v.grad_target() if v is not None else None for v in (self.gamma, self.beta))
+        if any(tt is None and v is not None for tt, v in zip(t, (self.gamma, self.beta))):
+            return None
+        return t
 
     def compute_output_shape(self, s):
         return s
+
+    def get_config(self):
+        cfg = dict(super().get_config(), axis=self.axis, epsilon=self.epsilon, center=self.center, scale=self.scale,
+                   rms_scaling=self.rms_scaling, beta_initializer=_init.serialize(self.beta_initializer),
+                   gamma_initializer=_init.serialize(self.gamma_initializer))
+        for k in ("beta_regularizer", "gamma_regularizer"):  # (only when set, as the other layers' configs)
+            if getattr(self, k) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
 
 
 class Embedding(Layer):
