@@ -44,6 +44,9 @@ HIP_FILE_FLAGS = {
     "grouped_conv.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # conv_transpose.hip: the same
     "conv_transpose.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # lstm.hip: the same for its gate math, and no contraction of its multiplies and adds into fma (the
+    # activations and the cell update are the sequence of roundings csrc/kernels/lstm.h states)
+    "lstm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-ffp-contract=off"],
 }
 
 

@@ -16,6 +16,7 @@
 #include "kernels/gemm_f32.h"
 #include "kernels/groupnorm.h"
 #include "kernels/layernorm.h"
+#include "kernels/lstm.h"
 #include "kernels/depthwise.h"
 #include "kernels/grouped_conv.h"
 #include "kernels/conv_transpose.h"
@@ -1662,6 +1663,113 @@ pybind11::dict ln_plan(int64_t R, int64_t C, bool bf16) {
   return d;
 }
 
+// ---- LSTM scan (kernels/lstm.h): zx [B,T,4U] (x W + b), r [U,4U], both f32 or both bf16; c / dc in f32
+struct LstmShape {
+  int64_t B, T, U;
+  bool bf16;
+};
+LstmShape lstm_check(const at::Tensor& zx, const at::Tensor& r, const char* what) {
+  TORCH_CHECK(zx.is_cuda() && zx.is_contiguous() && zx.dim() == 3, what, ": contiguous [B, T, 4U] GPU tensor expected");
+  TORCH_CHECK(zx.scalar_type() == at::kFloat || zx.scalar_type() == at::kBFloat16, what, ": float32 or bfloat16 expected");
+  TORCH_CHECK(zx.numel() > 0 && zx.size(2) % 4 == 0, what, ": empty tensor, or a last dimension that is not 4U");
+  LstmShape sh{zx.size(0), zx.size(1), zx.size(2) / 4, zx.scalar_type() == at::kBFloat16};
+  TORCH_CHECK(sh.U % 16 == 0 && sh.U <= tdl::kLstmMaxU, what, ": U must be a multiple of 16, at most ", tdl::kLstmMaxU);
+  TORCH_CHECK(zx.numel() < (int64_t(1) << 31), what, ": 2^31 elements or more");
+  TORCH_CHECK(r.is_cuda() && r.is_contiguous() && r.scalar_type() == zx.scalar_type() && r.dim() == 2 &&
+                  r.size(0) == sh.U && r.size(1) == 4 * sh.U,
+              what, ": recurrent kernel must be a contiguous [U, 4U] tensor of the data's dtype");
+  return sh;
+}
+// an optional contiguous [B, U] state of dtype dt: its pointer or null
+const void* lstm_state(const c10::optional<at::Tensor>& t, const LstmShape& sh, at::ScalarType dt, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == dt && t->dim() == 2 && t->size(0) == sh.B &&
+                  t->size(1) == sh.U,
+              what, ": states must be contiguous [B, U] (h in the data's dtype, c in f32)");
+  return t->data_ptr();
+}
+void lstm_dims(tdl::LstmArgs& a, const LstmShape& sh, bool rev) {
+  a.B = (int)sh.B, a.T = (int)sh.T, a.U = (int)sh.U, a.rev = rev ? 1 : 0;
+}
+
+// (hs [B,T,U], h_last [B,U], c_last f32 [B,U], gates [B,T,4U], cs f32 [B,T,U]); save = false: no gates / cs
+// (undefined).  Sequences are in processing order (go_backwards: reversed time)
+std::vector<at::Tensor> lstm_forward(at::Tensor zx, at::Tensor r, c10::optional<at::Tensor> h0,
+                                     c10::optional<at::Tensor> c0, bool go_backwards, bool save) {
+  const LstmShape sh = lstm_check(zx, r, "lstm_forward");
+  auto f = zx.options().dtype(at::kFloat);
+  auto rt = r.t().contiguous();  // R^T [4U][U], once per call
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rt.data_ptr()) % 16 == 0, "lstm_forward: unaligned allocation");
+  auto hs = fresh({sh.B, sh.T, sh.U}, zx.options());
+  auto hl = fresh({sh.B, sh.U}, zx.options());
+  auto cl = fresh({sh.B, sh.U}, f);
+  at::Tensor gates, cs;
+  if (save) {
+    gates = fresh({sh.B, sh.T, 4 * sh.U}, zx.options());
+    cs = fresh({sh.B, sh.T, sh.U}, f);
+  }
+  tdl::LstmArgs a{};
+  lstm_dims(a, sh, go_backwards);
+  a.zx = zx.data_ptr();
+  a.r = rt.data_ptr();
+  a.h0 = lstm_state(h0, sh, zx.scalar_type(), "lstm_forward");
+  a.c0 = (const float*)lstm_state(c0, sh, at::kFloat, "lstm_forward");
+  a.hs = hs.data_ptr(), a.h_last = hl.data_ptr(), a.c_last = cl.data_ptr<float>();
+  if (save) a.gates = gates.data_ptr(), a.cs = cs.data_ptr<float>();
+  tdl::lstm_forward(a, sh.bf16, cur_stream());
+  return {hs, hl, cl, gates, cs};
+}
+
+// (dz [B,T,4U], dh0, dc0 f32).  dhs [B,T,U] / dh_last [B,U] (the data's dtype) / dc_last f32 [B,U]: each optional;
+// want_state = false: no dh0 / dc0 (undefined)
+std::vector<at::Tensor> lstm_backward(at::Tensor gates, at::Tensor cs, at::Tensor r, c10::optional<at::Tensor> c0,
+                                      c10::optional<at::Tensor> dhs, c10::optional<at::Tensor> dh_last,
+                                      c10::optional<at::Tensor> dc_last, bool go_backwards, bool want_state) {
+  const LstmShape sh = lstm_check(gates, r, "lstm_backward");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(r.data_ptr()) % 16 == 0, "lstm_backward: 16-byte aligned recurrent kernel expected");
+  TORCH_CHECK(cs.is_cuda() && cs.is_contiguous() && cs.scalar_type() == at::kFloat && cs.dim() == 3 &&
+                  cs.size(0) == sh.B && cs.size(1) == sh.T && cs.size(2) == sh.U,
+              "lstm_backward: cs must be contiguous f32 [B, T, U]");
+  auto f = gates.options().dtype(at::kFloat);
+  tdl::LstmArgs a{};
+  lstm_dims(a, sh, go_backwards);
+  a.gates = gates.data_ptr(), a.cs = cs.data_ptr<float>(), a.r = r.data_ptr();
+  a.c0 = (const float*)lstm_state(c0, sh, at::kFloat, "lstm_backward");
+  if (dhs.has_value() && dhs->defined()) {
+    TORCH_CHECK(dhs->is_cuda() && dhs->is_contiguous() && dhs->scalar_type() == gates.scalar_type() && dhs->dim() == 3 &&
+                    dhs->size(0) == sh.B && dhs->size(1) == sh.T && dhs->size(2) == sh.U,
+                "lstm_backward: dhs must be contiguous [B, T, U] of the data's dtype");
+    a.dhs = dhs->data_ptr();
+  }
+  a.dh_last = lstm_state(dh_last, sh, gates.scalar_type(), "lstm_backward");
+  a.dc_last = (const float*)lstm_state(dc_last, sh, at::kFloat, "lstm_backward");
+  auto dz = fresh({sh.B, sh.T, 4 * sh.U}, gates.options());
+  at::Tensor dh0, dc0;
+  if (want_state) {
+    dh0 = fresh({sh.B, sh.U}, gates.options());
+    dc0 = fresh({sh.B, sh.U}, f);
+    a.dh0 = dh0.data_ptr(), a.dc0 = dc0.data_ptr<float>();
+  }
+  a.dz = dz.data_ptr();
+  tdl::lstm_backward(a, sh.bf16, cur_stream());
+  return {dz, dh0, dc0};
+}
+
+pybind11::dict lstm_plan(int64_t B, int64_t T, int64_t U, bool bf16) {
+  TORCH_CHECK(B >= 1 && T >= 1 && U >= 16 && U % 16 == 0 && U <= tdl::kLstmMaxU,
+              "lstm_plan: B, T >= 1 and U a multiple of 16 in [16, ", tdl::kLstmMaxU, "] expected");
+  const tdl::LstmPlan p = tdl::lstm_plan(B, T, (int)U, bf16);
+  pybind11::dict d;
+  d["resident"] = p.resident;
+  d["lds_bytes"] = p.lds_fwd;
+  d["lds_bytes_bwd"] = p.lds_bwd;
+  d["workgroups"] = p.workgroups;
+  d["tiles_wave"] = p.tiles_wave;
+  d["max_u"] = tdl::kLstmMaxU;
+  d["resident_max_u"] = p.resident_max_u;
+  return d;
+}
+
 // ---- depthwise convolution (kernels/depthwise.h): x [N,H,W,C], w f32 [kh,kw,C,dm], y [N,OH,OW,C*dm]
 // geo = (sh, sw, dh, dw, pt, pl)
 struct DwShape {
@@ -2192,6 +2300,16 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("dbeta_out") = pybind11::none(), pybind11::arg("want_params") = true);
   m.def("ln_plan", &ln_plan, "layer normalisation plan for (R, C, dtype) as a dict, with the plans' widths; no GPU needed",
         pybind11::arg("R"), pybind11::arg("C"), pybind11::arg("bf16"));
+  m.def("lstm_forward", &lstm_forward, "LSTM scan forward over zx = x W + b: (hs, h_last, c_last, gates, cs)",
+        pybind11::arg("zx"), pybind11::arg("r"), pybind11::arg("h0") = pybind11::none(),
+        pybind11::arg("c0") = pybind11::none(), pybind11::arg("go_backwards") = false, pybind11::arg("save") = true);
+  m.def("lstm_backward", &lstm_backward, "LSTM scan backward: (dz, dh0, dc0)",
+        pybind11::arg("gates"), pybind11::arg("cs"), pybind11::arg("r"), pybind11::arg("c0") = pybind11::none(),
+        pybind11::arg("dhs") = pybind11::none(), pybind11::arg("dh_last") = pybind11::none(),
+        pybind11::arg("dc_last") = pybind11::none(), pybind11::arg("go_backwards") = false,
+        pybind11::arg("want_state") = false);
+  m.def("lstm_plan", &lstm_plan, "LSTM scan plan for (B, T, U, dtype) as a dict, with the limits; no GPU needed",
+        pybind11::arg("B"), pybind11::arg("T"), pybind11::arg("U"), pybind11::arg("bf16"));
   m.def("dw_forward", &dw_forward, "channels-last depthwise convolution forward (+ bias, + ReLU): y",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("geo"), pybind11::arg("out_h"),
         pybind11::arg("out_w"), pybind11::arg("act") = 0, pybind11::arg("out") = pybind11::none());

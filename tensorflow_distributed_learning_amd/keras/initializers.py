@@ -150,11 +150,36 @@ class LecunNormal(_Preset):
         super().__init__(1.0, "fan_in", "truncated_normal", seed)
 
 
+class Orthogonal(Initializer):
+    """tf.keras.initializers.Orthogonal: the Q of a QR decomposition of a seeded normal matrix, its columns
+    sign-fixed by the diagonal of R, times ``gain``.  A shape of more than two axes is flattened to
+    ``[prod(shape[:-1]), shape[-1]]``; the columns (tall) or the rows (wide) are orthonormal."""
+
+    def __init__(self, gain=1.0, seed=None):
+        self.gain, self.seed = gain, seed
+
+    def __call__(self, shape, dtype=torch.float32):
+        shape = tuple(shape)
+        if len(shape) < 2:
+            raise ValueError("Orthogonal: a shape of at least two axes expected")
+        g = torch.Generator().manual_seed(self.seed) if self.seed is not None else _GEN
+        rows, cols = math.prod(shape[:-1]), shape[-1]
+        a = torch.randn((max(rows, cols), min(rows, cols)), generator=g, dtype=torch.float64)
+        q, r = torch.linalg.qr(a)
+        q = q * torch.sign(torch.diagonal(r))
+        if rows < cols:
+            q = q.t()
+        return (self.gain * q).reshape(shape).to(dtype)
+
+    def get_config(self):
+        return {"gain": self.gain, "seed": self.seed}
+
+
 _ALIASES = {
     "zeros": Zeros, "ones": Ones, "constant": Constant, "random_uniform": RandomUniform,
     "random_normal": RandomNormal, "truncated_normal": TruncatedNormal, "glorot_uniform": GlorotUniform,
     "glorot_normal": GlorotNormal, "he_normal": HeNormal, "he_uniform": HeUniform, "lecun_normal": LecunNormal,
-    "variance_scaling": VarianceScaling,
+    "variance_scaling": VarianceScaling, "orthogonal": Orthogonal,
 }
 
 

@@ -26,6 +26,7 @@ from ..ops import conv_transpose as _convt
 from ..ops import attention as _attn
 from ..ops import dense as _dense
 from ..ops import depthwise as _dw
+from ..ops import lstm as _lstm
 from . import activations as _act
 from . import initializers as _init
 
@@ -1729,6 +1730,109 @@ class MultiHeadAttention(_CallCounterRNG, Layer):
         return cfg
 
 
+class LSTM(Layer):
+    """tf.keras.layers.LSTM over ``[B, T, D]`` inputs: ``layer(x, initial_state=None, training=None)``.  Weights, with
+    Keras' names and shapes: ``kernel [D, 4U]``, ``recurrent_kernel [U, 4U]``, ``bias [4U]`` (gate columns
+    ``i, f, c, o``; the forget quarter starts at one with ``unit_forget_bias``).  The output is the last hidden state,
+    or every step's with ``return_sequences`` (in processing order: reversed time with ``go_backwards``);
+    ``return_state`` appends ``[h, c]``.
+
+    The input projection ``x W + b`` of all steps runs through Dense's dispatch (the f32 / bf16 MFMA GEMMs on the GPU,
+    gradients straight into the trainer's slab); the recurrence runs on the scan kernels of ops/lstm.py when the
+    activations are tanh / sigmoid, else (and on the CPU) on the same formula in PyTorch ops.  ``initial_state`` is for
+    eager and subclassed calls; ``dropout``, ``recurrent_dropout``, ``stateful``, ``unroll`` and ``mask`` are not
+    implemented."""
+
+    def __init__(self, units, activation="tanh", recurrent_activation="sigmoid", use_bias=True,
+                 kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
+                 unit_forget_bias=True, kernel_regularizer=None, recurrent_regularizer=None, bias_regularizer=None,
+                 return_sequences=False, return_state=False, go_backwards=False, stateful=False, unroll=False,
+                 dropout=0.0, recurrent_dropout=0.0, seed=None, **kw):
+        super().__init__(**kw)
+        for what, v in (("dropout", dropout), ("recurrent_dropout", recurrent_dropout), ("stateful", stateful),
+                        ("unroll", unroll)):
+            if v:
+                raise ValueError(f"LSTM: {what}={v!r} is not implemented")
+        self.units = int(units)
+        self.activation, self.recurrent_activation = _act.get(activation), _act.get(recurrent_activation)
+        self.use_bias, self.unit_forget_bias = bool(use_bias), bool(unit_forget_bias)
+        self.kernel_initializer = _init.get(kernel_initializer)
+        self.recurrent_initializer = _init.get(recurrent_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        self.kernel_regularizer = _regularizer_from(kernel_regularizer)
+        self.recurrent_regularizer = _regularizer_from(recurrent_regularizer)
+        self.bias_regularizer = _regularizer_from(bias_regularizer)
+        self.return_sequences, self.return_state = bool(return_sequences), bool(return_state)
+        self.go_backwards = bool(go_backwards)
+        self.seed = None if seed is None else int(seed)
+
+    def __call__(self, inputs, initial_state=None, training=None, mask=None):
+        """Packs ``[x, h0, c0]`` into the one input structure of Layer.__call__."""
+        if mask is not None:
+            raise ValueError("LSTM: mask is not implemented")
+        if initial_state is not None:
+            if isinstance(inputs, KerasTensor):
+                raise NotImplementedError("LSTM: initial_state in a functional model")
+            if len(initial_state) != 2:
+                raise ValueError("LSTM: initial_state must be [h0, c0]")
+            inputs = [inputs, initial_state[0], initial_state[1]]
+        return super().__call__(inputs, training=training)
+
+    def build(self, input_shape):
+        if isinstance(input_shape, list):
+            input_shape = input_shape[0]
+        d, U = int(input_shape[-1]), self.units
+
+        def bias_init(shape, dtype=torch.float32):
+            b = self.bias_initializer(shape, dtype)
+            if self.unit_forget_bias:
+                b[U:2 * U] = 1.0
+            return b
+
+        self.kernel = self.add_weight("kernel", (d, 4 * U), initializer=self.kernel_initializer,
+                                      regularizer=self.kernel_regularizer)
+        self.recurrent_kernel = self.add_weight("recurrent_kernel", (U, 4 * U), initializer=self.recurrent_initializer,
+                                                regularizer=self.recurrent_regularizer)
+        self.bias = self.add_weight("bias", (4 * U,), initializer=bias_init,
+                                    regularizer=self.bias_regularizer) if self.use_bias else None
+        self.built = True
+
+    def _grad_targets(self):
+        """The recurrent kernel's slab view the backward adds dR into directly, or None."""
+        return self.recurrent_kernel.grad_target() if self.trainable else None
+
+    def call(self, inputs, training=None):
+        x, h0, c0 = inputs if isinstance(inputs, (list, tuple)) else (inputs, None, None)
+        if x.dim() != 3:
+            raise ValueError("LSTM: rank-3 [batch, time, features] input expected")
+        zx = _dense_rows(x, self.kernel, self.bias, 4 * self.units, _act.linear)
+        standard = self.activation is _act.tanh and self.recurrent_activation is _act.sigmoid
+        gt = self._grad_targets() if standard and _lstm.supported(zx) and not _lstm.use_torch() else None
+        hs, h, c = _lstm.lstm_scan(zx, self.recurrent_kernel.value, h0, c0, self.go_backwards, gt, self.activation,
+                                   self.recurrent_activation, standard)
+        out = hs if self.return_sequences else h
+        return [out, h, c.to(h.dtype)] if self.return_state else out
+
+    def compute_output_shape(self, s):
+        if isinstance(s, list):
+            s = s[0]
+        out = (s[0], s[1], self.units) if self.return_sequences else (s[0], self.units)
+        return [out, (s[0], self.units), (s[0], self.units)] if self.return_state else out
+
+    def get_config(self):
+        cfg = dict(super().get_config(), units=self.units, activation=_act.serialize(self.activation),
+                   recurrent_activation=_act.serialize(self.recurrent_activation), use_bias=self.use_bias,
+                   kernel_initializer=_init.serialize(self.kernel_initializer),
+                   recurrent_initializer=_init.serialize(self.recurrent_initializer),
+                   bias_initializer=_init.serialize(self.bias_initializer), unit_forget_bias=self.unit_forget_bias,
+                   return_sequences=self.return_sequences, return_state=self.return_state,
+                   go_backwards=self.go_backwards, seed=self.seed)
+        for k in ("kernel_regularizer", "recurrent_regularizer", "bias_regularizer"):  # (only when set)
+            if getattr(self, k) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
+
+
 class _Merge(Layer):
     def compute_output_shape(self, shapes):
         return shapes[0]
@@ -1809,7 +1913,7 @@ LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
-    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, MultiHeadAttention, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, MultiHeadAttention, LSTM, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
 __all__ = sorted(LAYER_CLASSES) + ["Convolution2DTranspose", "Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]

@@ -1,0 +1,117 @@
+"""Training through keras.layers.LSTM on the GPU.  The model: Embedding -> LSTM(32, return_sequences) -> LSTM(16) ->
+Dense, T = 12, 6 SGD steps."""
+import os
+import subprocess
+import sys
+from unittest import mock
+
+import numpy as np
+import pytest
+import torch
+
+import tensorflow_distributed_learning_amd as tdl
+from tensorflow_distributed_learning_amd.ops import lstm as LS
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T, VOCAB, DIM, CLASSES, BATCH, STEPS, LR = 12, 50, 16, 5, 8, 6, 0.5
+
+
+def _data():
+    g = torch.Generator().manual_seed(0)
+    return (torch.randint(0, VOCAB, (STEPS * BATCH, T), generator=g, dtype=torch.int32),
+            torch.randint(0, CLASSES, (STEPS * BATCH,), generator=g, dtype=torch.int32))
+
+
+def _fit(env=None, policy="float32", steps=STEPS):
+    """(initial weights, final weights, model) of the fit; eager unless the caller asks for the graph."""
+    L = tdl.keras.layers
+    with mock.patch.dict(os.environ, dict({"TDL_DISABLE_FUSED": "1", "TDL_GRAPH_STEP": "0"}, **(env or {}))):
+        tdl.keras.backend.clear_session()
+        tdl.keras.utils.set_random_seed(3)
+        tdl.keras.mixed_precision.set_global_policy(policy)
+        try:
+            with tdl.distribute.MirroredStrategy(devices=["/gpu:0"]).scope():
+                m = tdl.keras.Sequential([L.Input((T,)), L.Embedding(VOCAB, DIM, name="emb"),
+                                          L.LSTM(32, return_sequences=True, name="lstm1"), L.LSTM(16, name="lstm2"),
+                                          L.Dense(CLASSES, name="head")])
+                m.compile(loss=tdl.keras.losses.SparseCategoricalCrossentropy(from_logits=True),
+                          optimizer=tdl.keras.optimizers.SGD(learning_rate=LR))
+            w0 = [np.array(w, np.float64) for w in m.get_weights()]
+            hist = m.fit(tdl.data.Dataset.from_tensor_slices(_data()).batch(BATCH).repeat(), epochs=1,
+                         steps_per_epoch=steps, verbose=0)
+            assert m._trainer.kind == "generic" and np.isfinite(hist.history["loss"]).all()
+            return w0, [np.array(w, np.float64) for w in m.get_weights()], m
+        finally:
+            tdl.keras.mixed_precision.set_global_policy("float32")
+
+
+def _fit_f64(w0):
+    """The same SGD steps in float64 on the CPU with the torch formulas; weights in the model's order:
+    emb, (kernel, recurrent_kernel, bias) of each LSTM, head kernel / bias."""
+    w = [torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in w0]
+    x, y = _data()
+    for s in range(STEPS):
+        xb, yb = x[s * BATCH:(s + 1) * BATCH].long(), y[s * BATCH:(s + 1) * BATCH].long()
+        h1 = LS.lstm_torch(w[0][xb] @ w[1] + w[3], w[2])[0]
+        h2 = LS.lstm_torch(h1 @ w[4] + w[6], w[5])[1]
+        loss = torch.nn.functional.cross_entropy(h2 @ w[7] + w[8], yb)
+        w = [(p - LR * g).detach().requires_grad_() for p, g in zip(w, torch.autograd.grad(loss, w))]
+    return [p.detach().numpy() for p in w]
+
+
+def _distance(a, b):
+    return max(float(np.abs(x - y).max()) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("policy", ["float32", "mixed_bfloat16"])
+def test_fit_runs_on_the_kernels_and_stays_as_close_to_f64_as_the_torch_formula(policy):
+    before, fb, by = LS.CALLS[0], LS.FALLBACKS[0], dict(LS.CALLS_BY_DTYPE)
+    w0, wk, m = _fit(policy=policy)
+    assert [a.shape for a in w0[1:4]] == [(DIM, 128), (32, 128), (128,)] and len(w0) == 9
+    assert LS.CALLS[0] >= before + 2 * STEPS and LS.FALLBACKS[0] == fb, "a fallback ran"
+    used = torch.bfloat16 if policy == "mixed_bfloat16" else torch.float32
+    assert LS.CALLS_BY_DTYPE[used] > by[used]
+    assert not any(np.array_equal(a, b) for a, b in zip(wk, w0))  # every weight moved
+    before = LS.CALLS[0]
+    w0t, wt, _ = _fit(policy=policy, env={"TDL_LSTM": "torch"})
+    assert LS.CALLS[0] == before and all(np.array_equal(a, b) for a, b in zip(w0, w0t))
+    ref = _fit_f64(w0)
+    dk, dt = _distance(wk, ref), _distance(wt, ref)
+    print(f"\n[lstm fit {policy}] distance to the f64 fit: kernels {dk:.3g}, torch formula {dt:.3g}; "
+          f"moved {_distance(ref, w0):.3g}")
+    assert _distance(ref, w0) > 1e-3 and dk <= 4 * dt
+
+
+def test_eager_step_launches_the_scan_kernels():
+    from tensorflow_distributed_learning_amd.utils.kernel_audit import audit
+
+    _, _, m = _fit(steps=1)  # warm-up (allocations, first-use set-up)
+    ds = tdl.data.Dataset.from_tensor_slices(_data()).batch(BATCH).repeat()
+    with mock.patch.dict(os.environ, {"TDL_DISABLE_FUSED": "1", "TDL_GRAPH_STEP": "0"}):
+        rep = audit(lambda: m.fit(ds, epochs=1, steps_per_epoch=1, verbose=0))
+    for kernel in ("k_lstm_fwd", "k_lstm_bwd"):
+        assert sum(c for n, c in rep["tdl"].items() if kernel in n) == 2, dict(rep["tdl"])
+    # no per-time-step torch kernels: nothing launches T times or more
+    assert not [n for cat in rep.values() for n, c in cat.items() if "sigmoid" in n.lower() or "tanh" in n.lower()]
+
+
+def _graph_fits():
+    # in a process of its own, as tests/test_layernorm_fit_gpu.py has it
+    for policy in ("float32", "mixed_bfloat16"):
+        before, fb = LS.CALLS[0], LS.FALLBACKS[0]
+        _, wg, g = _fit(policy=policy, env={"TDL_GRAPH_STEP": "1"})
+        _, we, e = _fit(policy=policy)
+        assert len(g._trainer._graphs) >= 1 and len(e._trainer._graphs) == 0, policy
+        assert LS.CALLS[0] > before and LS.FALLBACKS[0] == fb, policy
+        assert all(np.array_equal(x, y) for x, y in zip(wg, we)), policy
+
+
+def test_the_step_replays_in_a_captured_graph_and_equals_the_eager_fit():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, PYTHONPATH=ROOT),
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0 and "capture failed" not in r.stderr, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+if __name__ == "__main__":
+    _graph_fits()
