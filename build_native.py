@@ -47,6 +47,8 @@ HIP_FILE_FLAGS = {
     # lstm.hip: the same for its gate math, and no contraction of its multiplies and adds into fma (the
     # activations and the cell update are the sequence of roundings csrc/kernels/lstm.h states)
     "lstm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-ffp-contract=off"],
+    # gru.hip: the same two, for the sequence of roundings csrc/kernels/gru.h states
+    "gru.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-ffp-contract=off"],
 }
 
 

@@ -17,6 +17,7 @@
 #include "kernels/groupnorm.h"
 #include "kernels/layernorm.h"
 #include "kernels/lstm.h"
+#include "kernels/gru.h"
 #include "kernels/depthwise.h"
 #include "kernels/grouped_conv.h"
 #include "kernels/conv_transpose.h"
@@ -1770,6 +1771,116 @@ pybind11::dict lstm_plan(int64_t B, int64_t T, int64_t U, bool bf16) {
   return d;
 }
 
+// ---- GRU scan (kernels/gru.h): zx [B,T,3U] (x W + b_in), r [U,3U], both f32 or both bf16; b_rec f32 [3U]
+struct GruShape {
+  int64_t B, T, U;
+  bool bf16;
+};
+// x: a contiguous [B, T, planes * U] tensor of the scan (mx: 3 planes, the saved tensor: 4)
+GruShape gru_check(const at::Tensor& x, int planes, const at::Tensor& r, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 3, what, ": contiguous [B, T, ", planes, "U] GPU tensor expected");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16, what, ": float32 or bfloat16 expected");
+  TORCH_CHECK(x.numel() > 0 && x.size(2) % planes == 0, what, ": empty tensor, or a last dimension that is not ", planes, "U");
+  GruShape sh{x.size(0), x.size(1), x.size(2) / planes, x.scalar_type() == at::kBFloat16};
+  TORCH_CHECK(sh.U % 16 == 0 && sh.U <= tdl::kGruMaxU, what, ": U must be a multiple of 16, at most ", tdl::kGruMaxU);
+  TORCH_CHECK(sh.B * sh.T * 4 * sh.U < (int64_t(1) << 31), what, ": 2^31 elements or more");
+  TORCH_CHECK(r.is_cuda() && r.is_contiguous() && r.scalar_type() == x.scalar_type() && r.dim() == 2 &&
+                  r.size(0) == sh.U && r.size(1) == 3 * sh.U,
+              what, ": recurrent kernel must be a contiguous [U, 3U] tensor of the data's dtype");
+  return sh;
+}
+// an optional contiguous tensor of the given shape and the data's dtype: its pointer or null
+const void* gru_opt(const c10::optional<at::Tensor>& t, at::IntArrayRef shape, at::ScalarType dt, const char* what) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->scalar_type() == dt && t->sizes() == shape, what,
+              ": an optional tensor has the wrong shape, dtype or layout");
+  return t->data_ptr();
+}
+void gru_dims(tdl::GruArgs& a, const GruShape& sh, bool rev) {
+  a.B = (int)sh.B, a.T = (int)sh.T, a.U = (int)sh.U, a.rev = rev ? 1 : 0;
+}
+
+// (hs [B,T,U], h_last [B,U], saved [B,T,4U]: the planes z, r, hh, q); save = false: no saved tensor (undefined).
+// Sequences are in processing order (go_backwards: reversed time)
+std::vector<at::Tensor> gru_forward(at::Tensor zx, at::Tensor r, c10::optional<at::Tensor> b_rec,
+                                    c10::optional<at::Tensor> h0, bool go_backwards, bool save) {
+  const GruShape sh = gru_check(zx, 3, r, "gru_forward");
+  auto rt = r.t().contiguous();  // R^T [3U][U], once per call
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(rt.data_ptr()) % 16 == 0, "gru_forward: unaligned allocation");
+  auto hs = fresh({sh.B, sh.T, sh.U}, zx.options());
+  auto hl = fresh({sh.B, sh.U}, zx.options());
+  at::Tensor saved;
+  if (save) saved = fresh({sh.B, sh.T, 4 * sh.U}, zx.options());
+  tdl::GruArgs a{};
+  gru_dims(a, sh, go_backwards);
+  a.zx = zx.data_ptr();
+  a.r = rt.data_ptr();
+  a.b_rec = (const float*)gru_opt(b_rec, {3 * sh.U}, at::kFloat, "gru_forward");
+  a.h0 = gru_opt(h0, {sh.B, sh.U}, zx.scalar_type(), "gru_forward");
+  a.hs = hs.data_ptr(), a.h_last = hl.data_ptr();
+  if (save) a.saved = saved.data_ptr();
+  tdl::gru_forward(a, sh.bf16, cur_stream());
+  return {hs, hl, saved};
+}
+
+// (dzx [B,T,3U], dzh [B,T,3U], dh0).  dhs [B,T,U] / dh_last [B,U] (the data's dtype): each optional;
+// want_dh0 = false: no dh0 (undefined)
+std::vector<at::Tensor> gru_backward(at::Tensor saved, at::Tensor hs, at::Tensor r, c10::optional<at::Tensor> h0,
+                                     c10::optional<at::Tensor> dhs, c10::optional<at::Tensor> dh_last,
+                                     bool go_backwards, bool want_dh0) {
+  const GruShape sh = gru_check(saved, 4, r, "gru_backward");
+  const auto dt = saved.scalar_type();
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(r.data_ptr()) % 16 == 0, "gru_backward: 16-byte aligned recurrent kernel expected");
+  c10::optional<at::Tensor> hso(hs);
+  tdl::GruArgs a{};
+  gru_dims(a, sh, go_backwards);
+  a.saved = saved.data_ptr(), a.r = r.data_ptr();
+  a.hs = const_cast<void*>(gru_opt(hso, {sh.B, sh.T, sh.U}, dt, "gru_backward"));
+  a.h0 = gru_opt(h0, {sh.B, sh.U}, dt, "gru_backward");
+  a.dhs = gru_opt(dhs, {sh.B, sh.T, sh.U}, dt, "gru_backward");
+  a.dh_last = gru_opt(dh_last, {sh.B, sh.U}, dt, "gru_backward");
+  auto dzx = fresh({sh.B, sh.T, 3 * sh.U}, saved.options());
+  auto dzh = fresh({sh.B, sh.T, 3 * sh.U}, saved.options());
+  at::Tensor dh0;
+  if (want_dh0) {
+    dh0 = fresh({sh.B, sh.U}, saved.options());
+    a.dh0 = dh0.data_ptr();
+  }
+  a.dzx = dzx.data_ptr(), a.dzh = dzh.data_ptr();
+  tdl::gru_backward(a, sh.bf16, cur_stream());
+  return {dzx, dzh, dh0};
+}
+
+// db_rec: the f32 column sums of dzh [..., N] over all its rows, in a fixed order; added into `out` f32 [N] when given
+at::Tensor gru_bias_grad(at::Tensor dzh, c10::optional<at::Tensor> out) {
+  TORCH_CHECK(dzh.is_cuda() && dzh.is_contiguous() && dzh.dim() >= 1 && dzh.numel() > 0 &&
+                  (dzh.scalar_type() == at::kFloat || dzh.scalar_type() == at::kBFloat16),
+              "gru_bias_grad: non-empty contiguous f32 / bf16 GPU tensor expected");
+  const int64_t cols = dzh.size(-1), rows = dzh.numel() / cols;
+  TORCH_CHECK(dzh.numel() < (int64_t(1) << 31), "gru_bias_grad: 2^31 elements or more");
+  const bool acc = out.has_value() && out->defined();
+  at::Tensor o = acc ? *out : at::empty({cols}, dzh.options().dtype(at::kFloat));
+  TORCH_CHECK(o.is_cuda() && o.is_contiguous() && o.scalar_type() == at::kFloat && o.numel() == cols,
+              "gru_bias_grad: out must be a contiguous f32 [N] GPU tensor");
+  tdl::gru_colsum(dzh.data_ptr(), dzh.scalar_type() == at::kBFloat16, rows, (int)cols, o.data_ptr<float>(), acc, cur_stream());
+  return o;
+}
+
+pybind11::dict gru_plan(int64_t B, int64_t T, int64_t U, bool bf16) {
+  TORCH_CHECK(B >= 1 && T >= 1 && U >= 16 && U % 16 == 0 && U <= tdl::kGruMaxU,
+              "gru_plan: B, T >= 1 and U a multiple of 16 in [16, ", tdl::kGruMaxU, "] expected");
+  const tdl::GruPlan p = tdl::gru_plan(B, T, (int)U, bf16);
+  pybind11::dict d;
+  d["resident"] = p.resident;
+  d["lds_fwd"] = p.lds_fwd;
+  d["lds_bwd"] = p.lds_bwd;
+  d["workgroups"] = p.workgroups;
+  d["tiles_wave"] = p.tiles_wave;
+  d["resident_max_u"] = p.resident_max_u;
+  d["max_u"] = tdl::kGruMaxU;
+  return d;
+}
+
 // ---- depthwise convolution (kernels/depthwise.h): x [N,H,W,C], w f32 [kh,kw,C,dm], y [N,OH,OW,C*dm]
 // geo = (sh, sw, dh, dw, pt, pl)
 struct DwShape {
@@ -2309,6 +2420,17 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("dc_last") = pybind11::none(), pybind11::arg("go_backwards") = false,
         pybind11::arg("want_state") = false);
   m.def("lstm_plan", &lstm_plan, "LSTM scan plan for (B, T, U, dtype) as a dict, with the limits; no GPU needed",
+        pybind11::arg("B"), pybind11::arg("T"), pybind11::arg("U"), pybind11::arg("bf16"));
+  m.def("gru_forward", &gru_forward, "GRU scan forward over zx = x W + b_in: (hs, h_last, saved)",
+        pybind11::arg("zx"), pybind11::arg("r"), pybind11::arg("b_rec") = pybind11::none(),
+        pybind11::arg("h0") = pybind11::none(), pybind11::arg("go_backwards") = false, pybind11::arg("save") = true);
+  m.def("gru_backward", &gru_backward, "GRU scan backward: (dzx, dzh, dh0)",
+        pybind11::arg("saved"), pybind11::arg("hs"), pybind11::arg("r"), pybind11::arg("h0") = pybind11::none(),
+        pybind11::arg("dhs") = pybind11::none(), pybind11::arg("dh_last") = pybind11::none(),
+        pybind11::arg("go_backwards") = false, pybind11::arg("want_dh0") = false);
+  m.def("gru_bias_grad", &gru_bias_grad, "GRU recurrent-bias gradient: f32 column sums of dzh, added into out when given",
+        pybind11::arg("dzh"), pybind11::arg("out") = pybind11::none());
+  m.def("gru_plan", &gru_plan, "GRU scan plan for (B, T, U, dtype) as a dict, with the limits; no GPU needed",
         pybind11::arg("B"), pybind11::arg("T"), pybind11::arg("U"), pybind11::arg("bf16"));
   m.def("dw_forward", &dw_forward, "channels-last depthwise convolution forward (+ bias, + ReLU): y",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("bias"), pybind11::arg("geo"), pybind11::arg("out_h"),

@@ -27,6 +27,7 @@ from ..ops import attention as _attn
 from ..ops import dense as _dense
 from ..ops import depthwise as _dw
 from ..ops import lstm as _lstm
+from ..ops import gru as _gru
 from . import activations as _act
 from . import initializers as _init
 
@@ -1833,6 +1834,122 @@ class LSTM(Layer):
         return cfg
 
 
+class _BiasRow:
+    """Row ``row`` of a 2-D bias variable with the members ``_dense_rows`` reads of a bias: a contiguous view of the
+    value and of the gradient target."""
+
+    def __init__(self, var, row):
+        self._var, self._row = var, row
+
+    @property
+    def value(self):
+        return self._var.value[self._row]
+
+    def grad_target(self):
+        g = self._var.grad_target()
+        return None if g is None else g[self._row]
+
+
+class GRU(Layer):
+    """tf.keras.layers.GRU over ``[B, T, D]`` inputs: ``layer(x, initial_state=None, training=None)``.  Weights, with
+    Keras' names and shapes: ``kernel [D, 3U]``, ``recurrent_kernel [U, 3U]`` (gate columns ``z, r, h``) and ``bias
+    [2, 3U]`` with ``reset_after=True`` (row 0 the input bias, row 1 the recurrent bias), ``[3U]`` with
+    ``reset_after=False``.  The output is the last hidden state, or every step's with ``return_sequences`` (in
+    processing order: reversed time with ``go_backwards``); ``return_state`` appends ``[h]``.
+
+    The input projection ``x W + b_in`` of all steps runs through Dense's dispatch; the recurrence runs on the scan
+    kernels of ops/gru.py when ``reset_after`` is set and the activations are tanh / sigmoid, else (and on the CPU) on
+    the same formula in PyTorch ops.  ``initial_state`` is for eager and subclassed calls; ``dropout``,
+    ``recurrent_dropout``, ``stateful``, ``unroll`` and ``mask`` are not implemented."""
+
+    def __init__(self, units, activation="tanh", recurrent_activation="sigmoid", use_bias=True,
+                 kernel_initializer="glorot_uniform", recurrent_initializer="orthogonal", bias_initializer="zeros",
+                 kernel_regularizer=None, recurrent_regularizer=None, bias_regularizer=None,
+                 return_sequences=False, return_state=False, go_backwards=False, stateful=False, unroll=False,
+                 dropout=0.0, recurrent_dropout=0.0, reset_after=True, seed=None, **kw):
+        super().__init__(**kw)
+        for what, v in (("dropout", dropout), ("recurrent_dropout", recurrent_dropout), ("stateful", stateful),
+                        ("unroll", unroll)):
+            if v:
+                raise ValueError(f"GRU: {what}={v!r} is not implemented")
+        self.units = int(units)
+        self.activation, self.recurrent_activation = _act.get(activation), _act.get(recurrent_activation)
+        self.use_bias, self.reset_after = bool(use_bias), bool(reset_after)
+        self.kernel_initializer = _init.get(kernel_initializer)
+        self.recurrent_initializer = _init.get(recurrent_initializer)
+        self.bias_initializer = _init.get(bias_initializer)
+        self.kernel_regularizer = _regularizer_from(kernel_regularizer)
+        self.recurrent_regularizer = _regularizer_from(recurrent_regularizer)
+        self.bias_regularizer = _regularizer_from(bias_regularizer)
+        self.return_sequences, self.return_state = bool(return_sequences), bool(return_state)
+        self.go_backwards = bool(go_backwards)
+        self.seed = None if seed is None else int(seed)
+
+    def __call__(self, inputs, initial_state=None, training=None, mask=None):
+        """Packs ``[x, h0]`` into the one input structure of Layer.__call__."""
+        if mask is not None:
+            raise ValueError("GRU: mask is not implemented")
+        if initial_state is not None:
+            if isinstance(inputs, KerasTensor):
+                raise NotImplementedError("GRU: initial_state in a functional model")
+            if isinstance(initial_state, (list, tuple)):
+                if len(initial_state) != 1:
+                    raise ValueError("GRU: initial_state must be [h0] or h0")
+                initial_state = initial_state[0]
+            inputs = [inputs, initial_state]
+        return super().__call__(inputs, training=training)
+
+    def build(self, input_shape):
+        if isinstance(input_shape, list):
+            input_shape = input_shape[0]
+        d, U = int(input_shape[-1]), self.units
+        self.kernel = self.add_weight("kernel", (d, 3 * U), initializer=self.kernel_initializer,
+                                      regularizer=self.kernel_regularizer)
+        self.recurrent_kernel = self.add_weight("recurrent_kernel", (U, 3 * U), initializer=self.recurrent_initializer,
+                                                regularizer=self.recurrent_regularizer)
+        self.bias = self.add_weight("bias", (2, 3 * U) if self.reset_after else (3 * U,),
+                                    initializer=self.bias_initializer,
+                                    regularizer=self.bias_regularizer) if self.use_bias else None
+        self.built = True
+
+    def call(self, inputs, training=None):
+        x, h0 = inputs if isinstance(inputs, (list, tuple)) else (inputs, None)
+        if x.dim() != 3:
+            raise ValueError("GRU: rank-3 [batch, time, features] input expected")
+        two = self.bias is not None and self.reset_after  # input bias and recurrent bias: the variable's rows
+        zx = _dense_rows(x, self.kernel, _BiasRow(self.bias, 0) if two else self.bias, 3 * self.units, _act.linear)
+        standard = self.activation is _act.tanh and self.recurrent_activation is _act.sigmoid
+        rt = bt = None
+        if standard and self.reset_after and self.trainable and _gru.supported(zx) and not _gru.use_torch():
+            # the slab views the backward adds dR and db_rec into directly
+            rt = self.recurrent_kernel.grad_target()
+            bt = _BiasRow(self.bias, 1).grad_target() if two else None
+        hs, h = _gru.gru_scan(zx, self.recurrent_kernel.value, self.bias.value[1] if two else None, h0,
+                              self.go_backwards, rt, bt, self.activation, self.recurrent_activation, self.reset_after,
+                              standard)
+        out = hs if self.return_sequences else h
+        return [out, h] if self.return_state else out
+
+    def compute_output_shape(self, s):
+        if isinstance(s, list):
+            s = s[0]
+        out = (s[0], s[1], self.units) if self.return_sequences else (s[0], self.units)
+        return [out, (s[0], self.units)] if self.return_state else out
+
+    def get_config(self):
+        cfg = dict(super().get_config(), units=self.units, activation=_act.serialize(self.activation),
+                   recurrent_activation=_act.serialize(self.recurrent_activation), use_bias=self.use_bias,
+                   kernel_initializer=_init.serialize(self.kernel_initializer),
+                   recurrent_initializer=_init.serialize(self.recurrent_initializer),
+                   bias_initializer=_init.serialize(self.bias_initializer), return_sequences=self.return_sequences,
+                   return_state=self.return_state, go_backwards=self.go_backwards, reset_after=self.reset_after,
+                   seed=self.seed)
+        for k in ("kernel_regularizer", "recurrent_regularizer", "bias_regularizer"):  # (only when set)
+            if getattr(self, k) is not None:
+                cfg[k] = GroupNormalization._regularizer_config(getattr(self, k))
+        return cfg
+
+
 class _Merge(Layer):
     def compute_output_shape(self, shapes):
         return shapes[0]
@@ -1913,7 +2030,7 @@ LAYER_CLASSES = {c.__name__: c for c in (
     InputLayer, Dense, Conv2D, DepthwiseConv2D, SeparableConv2D, Conv2DTranspose, MaxPooling2D, AveragePooling2D, GlobalAveragePooling2D, GlobalMaxPooling2D, Flatten,
     Reshape, Activation, ReLU, Softmax, Dropout, SpatialDropout2D, RandomFlip, RandomCrop, RandomTranslation, Rescaling,
     ZeroPadding2D, BatchNormalization,
-    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, MultiHeadAttention, LSTM, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
+    SyncBatchNormalization, GroupNormalization, LayerNormalization, Embedding, MultiHeadAttention, LSTM, GRU, Add, Subtract, Multiply, Average, Maximum, Concatenate)}
 
 # the layer classes and the functional-API entry points (what ``from ...keras.layers import *`` gives)
 __all__ = sorted(LAYER_CLASSES) + ["Convolution2DTranspose", "Layer", "Input", "KerasTensor", "add", "concatenate", "multiply"]
