@@ -12,6 +12,7 @@
 #include "kernels/conv.h"
 #include "kernels/augment.h"
 #include "kernels/dropout.h"
+#include "kernels/embedding.h"
 #include "kernels/gemm.h"
 #include "kernels/gemm_f32.h"
 #include "kernels/groupnorm.h"
@@ -1664,6 +1665,85 @@ pybind11::dict ln_plan(int64_t R, int64_t C, bool bf16) {
   return d;
 }
 
+// ---- embedding (kernels/embedding.h): ids [...] int32 / int64, table [V, D] f32 (or its bf16 copy), y / dy [..., D]
+struct EmbShape {
+  int64_t N, V, D;
+  bool ids64;
+  tdl::EmbPlan plan;
+};
+EmbShape emb_check(const at::Tensor& ids, int64_t V, int64_t D, bool bf16, const char* what) {
+  TORCH_CHECK(ids.is_cuda() && ids.is_contiguous(), what, ": contiguous GPU ids expected");
+  TORCH_CHECK(ids.scalar_type() == at::kInt || ids.scalar_type() == at::kLong, what, ": int32 or int64 ids expected");
+  EmbShape sh;
+  sh.N = ids.numel();
+  sh.V = V;
+  sh.D = D;
+  sh.ids64 = ids.scalar_type() == at::kLong;
+  TORCH_CHECK(sh.N >= 1 && V >= 1 && D >= 1 && D <= tdl::kEmbMaxD, what, ": N >= 1, V >= 1 and 1 <= D <= ", tdl::kEmbMaxD,
+              " expected");
+  const int64_t lim = int64_t(1) << 31;
+  TORCH_CHECK(sh.N * D < lim && V * D < lim, what, ": tensors of 2^31 elements and more");
+  sh.plan = tdl::embed_plan(sh.N, V, (int)D, bf16);
+  TORCH_CHECK(sh.plan.fwd_blocks < tdl::kEmbMaxBlocks && sh.plan.ranges < tdl::kEmbMaxBlocks &&
+                  (sh.N + tdl::kEmbCountThreads - 1) / tdl::kEmbCountThreads < tdl::kEmbMaxBlocks,
+              what, ": 2^24 workgroups or more");
+  return sh;
+}
+
+// y [ids.shape..., D] = table[ids]; an id outside [0, V) gives a zero row.  table f32, or bf16 with out_bf16
+at::Tensor embed_forward(at::Tensor ids, at::Tensor table, bool out_bf16) {
+  TORCH_CHECK(table.is_cuda() && table.is_contiguous() && table.dim() == 2, "embed_forward: contiguous [V, D] GPU table expected");
+  const bool tb = table.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(table.scalar_type() == at::kFloat || (tb && out_bf16), "embed_forward: f32 table, or bf16 table and bf16 output");
+  const EmbShape sh = emb_check(ids, table.size(0), table.size(1), out_bf16, "embed_forward");
+  auto shape = ids.sizes().vec();
+  shape.push_back(sh.D);
+  auto y = fresh(shape, table.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  tdl::embed_forward(ids.data_ptr(), sh.ids64, table.data_ptr(), tb, y.data_ptr(), out_bf16, sh.N, sh.V, (int)sh.D,
+                     cur_stream());
+  return y;
+}
+
+// dE [V, D] f32: the ordered fold of kernels/embedding.h.  target: a contiguous f32 [V, D] tensor (a trainer's slab
+// view) the gradient is ADDED into; it is then what is returned
+at::Tensor embed_backward(at::Tensor ids, at::Tensor dy, int64_t V, c10::optional<at::Tensor> target) {
+  TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.dim() >= 1, "embed_backward: contiguous GPU dy expected");
+  const bool bf = dy.scalar_type() == at::kBFloat16;
+  TORCH_CHECK(dy.scalar_type() == at::kFloat || bf, "embed_backward: float32 or bfloat16 dy expected");
+  const int64_t D = dy.size(-1);
+  const EmbShape sh = emb_check(ids, V, D, bf, "embed_backward");
+  TORCH_CHECK(dy.numel() == sh.N * D, "embed_backward: dy must be [ids.shape..., D]");
+  const bool tgt = target.has_value() && target->defined();
+  if (tgt)
+    TORCH_CHECK(target->is_cuda() && target->is_contiguous() && target->scalar_type() == at::kFloat &&
+                    target->dim() == 2 && target->size(0) == V && target->size(1) == D,
+                "embed_backward: the target must be a contiguous f32 [V, D] GPU tensor");
+  auto out = tgt ? *target : fresh({V, D}, dy.options().dtype(at::kFloat));
+  auto counts = at::zeros({sh.plan.ranges}, dy.options().dtype(at::kInt));  // the zeroed workspace of k_embed_count
+  tdl::embed_backward(ids.data_ptr(), sh.ids64, dy.data_ptr(), bf, out.data_ptr<float>(), tgt, counts.data_ptr<int>(),
+                      sh.N, V, (int)D, cur_stream());
+  return out;
+}
+
+pybind11::dict embed_plan(int64_t N, int64_t V, int64_t D, bool bf16) {
+  TORCH_CHECK(N >= 1 && V >= 1 && D >= 1 && D <= tdl::kEmbMaxD, "embed_plan: N >= 1, V >= 1 and 1 <= D <= ",
+              tdl::kEmbMaxD, " expected");
+  const tdl::EmbPlan p = tdl::embed_plan(N, V, (int)D, bf16);
+  pybind11::dict d;
+  d["vec"] = p.vec;
+  d["lanes_fwd"] = p.L;
+  d["rows_per_wave_fwd"] = p.rows_per_wave_fwd;
+  d["fwd_blocks"] = p.fwd_blocks;
+  d["rows_wg"] = p.rows_wg;
+  d["ranges"] = p.ranges;
+  d["queue"] = tdl::kEmbQueue;
+  d["scan_block"] = tdl::kEmbScanBlock;
+  d["lds_bwd"] = p.lds_bwd;
+  d["max_d"] = tdl::kEmbMaxD;
+  d["max_blocks"] = tdl::kEmbMaxBlocks;
+  return d;
+}
+
 // ---- LSTM scan (kernels/lstm.h): zx [B,T,4U] (x W + b), r [U,4U], both f32 or both bf16; c / dc in f32
 struct LstmShape {
   int64_t B, T, U;
@@ -2411,6 +2491,13 @@ void register_ops(pybind11::module& m) {
         pybind11::arg("dbeta_out") = pybind11::none(), pybind11::arg("want_params") = true);
   m.def("ln_plan", &ln_plan, "layer normalisation plan for (R, C, dtype) as a dict, with the plans' widths; no GPU needed",
         pybind11::arg("R"), pybind11::arg("C"), pybind11::arg("bf16"));
+  m.def("embed_forward", &embed_forward, "y = table[ids] (a zero row for an id outside [0, V)); f32 or bf16 output",
+        pybind11::arg("ids"), pybind11::arg("table"), pybind11::arg("out_bf16") = false);
+  m.def("embed_backward", &embed_backward, "dE [V, D] f32: per row the ordered f32 sum of dy over its tokens; added "
+        "into target (which is returned) when given", pybind11::arg("ids"), pybind11::arg("dy"), pybind11::arg("V"),
+        pybind11::arg("target") = pybind11::none());
+  m.def("embed_plan", &embed_plan, "embedding plan for (N, V, D, dtype) as a dict, with the limits; no GPU needed",
+        pybind11::arg("N"), pybind11::arg("V"), pybind11::arg("D"), pybind11::arg("bf16"));
   m.def("lstm_forward", &lstm_forward, "LSTM scan forward over zx = x W + b: (hs, h_last, c_last, gates, cs)",
         pybind11::arg("zx"), pybind11::arg("r"), pybind11::arg("h0") = pybind11::none(),
         pybind11::arg("c0") = pybind11::none(), pybind11::arg("go_backwards") = false, pybind11::arg("save") = true);

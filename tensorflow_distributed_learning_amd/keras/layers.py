@@ -1594,20 +1594,50 @@ class LayerNormalization(Layer):
 
 
 class Embedding(Layer):
-    def __init__(self, input_dim, output_dim, embeddings_initializer="uniform", **kw):
+    """tf.keras.layers.Embedding: ``embeddings[ids]`` for integer ``ids`` of any shape.  On the GPU the lookup and its
+    gradient run on the hand-written kernels (ops/embedding.py): int32 or int64 ids as they come, the result in the
+    layer's compute dtype (bf16 under ``mixed_bfloat16``: the f32 row rounded once), the gradient a fixed-order sum
+    added straight into the trainer's slab, and an id outside ``[0, input_dim)`` a row of zeros.  On the CPU the layer
+    is ``F.embedding``.  ``mask_zero=True`` raises (no mask propagation); ``input_length`` is accepted and ignored."""
+
+    def __init__(self, input_dim, output_dim, embeddings_initializer="uniform", embeddings_regularizer=None,
+                 mask_zero=False, input_length=None, **kw):
         super().__init__(**kw)
+        if mask_zero:
+            raise NotImplementedError("Embedding: mask_zero=True is not implemented (no mask propagation)")
         self.input_dim, self.output_dim = int(input_dim), int(output_dim)
         self.emb_init = _init.get("random_uniform" if embeddings_initializer == "uniform" else embeddings_initializer)
+        self.embeddings_regularizer = GroupNormalization._regularizer(embeddings_regularizer)
+        self.input_length = input_length
 
     def build(self, input_shape):
-        self.embeddings = self.add_weight("embeddings", (self.input_dim, self.output_dim), initializer=self.emb_init)
+        self.embeddings = self.add_weight("embeddings", (self.input_dim, self.output_dim), initializer=self.emb_init,
+                                          regularizer=self.embeddings_regularizer)
         self.built = True
 
     def call(self, x, training=None):
-        return F.embedding(x.long(), self.embeddings.value)
+        from ..ops import embedding as _emb
+
+        table = self.embeddings.value
+        if not x.is_cuda:
+            return _emb.embedding_torch(x, table)
+        out_dtype = _autocast_input(table.detach()[:0]).dtype  # the compute dtype of an f32 tensor here
+        gt = self.embeddings.grad_target() if self.trainable else None
+        if gt is None:
+            return _emb.embedding(x, table, out_dtype)
+        return _emb.embedding(x, table.detach(), out_dtype, grad_out=gt, anchor=table,
+                              table_bf16=self.embeddings.compute_view(torch.bfloat16))
 
     def compute_output_shape(self, s):
         return tuple(s) + (self.output_dim,)
+
+    def get_config(self):
+        cfg = dict(super().get_config(), input_dim=self.input_dim, output_dim=self.output_dim,
+                   embeddings_initializer=_init.serialize(self.emb_init), mask_zero=False,
+                   input_length=self.input_length)
+        if self.embeddings_regularizer is not None:  # (only when set, as the other layers' configs)
+            cfg["embeddings_regularizer"] = GroupNormalization._regularizer_config(self.embeddings_regularizer)
+        return cfg
 
 
 class MultiHeadAttention(_CallCounterRNG, Layer):
